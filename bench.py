@@ -6,7 +6,8 @@ training at seq_len 128, batch 32, bf16 compute, on synthetic CICIDS2017-shaped
 flows rendered to text (random-init weights), one client per GPU -- plus the
 aggregated test F1 after 3 local epochs + 1 FedAvg round.
 
-Two phases, one process per GPU:
+Two phases, one process per GPU; a plain run does phase 1 only and prints its line, ``--full``
+adds the FedAvg round / all-reduce timings of an N > 1 job and phase 2:
 
 1. Throughput (timed).  A "step" is the full reference step (client1.py:102-112):
    forward, CE loss, backward, Adam update -- here the fused HIP kernels replayed
@@ -17,7 +18,7 @@ Two phases, one process per GPU:
    communication is charged once per K steps (the reference averages once per 3
    epochs = 1,270 steps at bs32, so this over-charges it).  The batches are the
    client's real training split (below).
-2. Quality (untimed, after the timed window).  The real BASELINE.json config-2/3
+2. Quality (``--full``; untimed, after the timed window).  The real BASELINE.json config-2/3
    protocol through the framework's own federated client (fed/runner.py):
    a 225,745-row synthetic CICIDS2017 file, a 10 % sample per client (seed
    42 + client), 60/20/20 split (13,544 / 4,515 / 4,515 rows), 3 local epochs of
@@ -26,7 +27,10 @@ Two phases, one process per GPU:
    client's 4,515 test rows (client1.py:379-401; reference numbers
    client1_aggregated_metrics.csv:2 / client2_aggregated_metrics.csv:2).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+``--dump-outputs DIR`` writes what the last timed step gave its caller (its loss, the mean loss
+of the window, a fixed seeded sample of the updated fp32 weights) as DIR/<name>.npy; the data,
+the init and the batch order are seeded, so two runs with the same arguments see the same inputs.
 With --gpus N > 1 and no torch.distributed environment, bench.py starts
 ``python -m torch.distributed.run --nproc-per-node N`` as a CHILD process
 (before any GPU call; the parent never touches the GPU) and exits with its
@@ -67,8 +71,15 @@ def _args(argv=None):
                          "runs the first ~100 ms of work measurably slower); no model state is touched")
     ap.add_argument("--step-events", action="store_true",
                     help="diagnostic: per-step GPU times from events recorded between the timed steps")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the FedAvg "
+                         "round / all-reduce timings (N > 1) and the 3-epoch + FedAvg quality protocol")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned and left behind as "
+                         "DIR/<name>.npy (float32): train: loss, mean_loss, params_sample (a fixed seeded "
+                         "sample of the updated fp32 weights); infer: probs")
     ap.add_argument("--no-quality", action="store_true",
-                    help="skip the post-timing 3-epoch + FedAvg quality protocol (kernel profiles of the step alone)")
+                    help="with --full: skip the post-timing 3-epoch + FedAvg quality protocol")
     ap.add_argument("--quality-rows", type=int, default=None,
                     help="rows of the synthetic file the quality protocol samples 10 %% of "
                          "(default 225,745 on GPU = the Friday-DDoS file; 2,000 on CPU)")
@@ -354,7 +365,10 @@ def main():
     real_frac = (sum(tok) / (len(tok) * B * S)) if tok else 1.0
     rows_frac = (sum(model.packed_rows(t, B, S) for t in tok) / (len(tok) * B * S)) \
         if tok and model.unpad and args.impl == "hip" else 1.0
-    comm_stats = _fedavg_timing(model, di, fedavg, comm, ncomm, k, sync)
+    if args.dump_outputs and di.is_main:
+        _dump_outputs(args.dump_outputs, {"loss": out, "mean_loss": torch.tensor(loss),
+                                          "params_sample": _sample(model.arena.master)})
+    comm_stats = _fedavg_timing(model, di, fedavg, comm, ncomm, k, sync) if args.full else {}
     graphs = len(getattr(step, "graphs", {}))
     graph_ok = step.graph is not None
     graph_chain = step.graph_count
@@ -366,9 +380,11 @@ def main():
         torch.cuda.empty_cache()
 
     # ---- quality: 3 local epochs + 1 FedAvg round through the federated client (untimed)
-    quality = {} if args.no_quality else _quality(client, di, comm, q_rows, q_epochs, on_gpu,
-                                                  n_virtual=args.virtual_clients, n_rounds=args.rounds,
-                                                  warm_epochs=args.warm_start_epochs)
+    # (--full only: a plain run stops at its headline figure)
+    quality = {} if args.no_quality or not args.full else _quality(client, di, comm, q_rows, q_epochs, on_gpu,
+                                                                   n_virtual=args.virtual_clients,
+                                                                   n_rounds=args.rounds,
+                                                                   warm_epochs=args.warm_start_epochs)
     n = di.world_size
     clients = topo.num_clients
     per_client = args.steps / dt
@@ -437,6 +453,22 @@ def main():
 
 
 REF_STEPS_PER_ROUND = 3 * 847  # local steps per FedAvg round in the reference (client1_terminal_output.txt:7-11)
+DUMP_SAMPLE = 8 * 1024 * 1024  # elements of a larger output kept by --dump-outputs (32 MB of float32)
+
+
+def _sample(t: torch.Tensor) -> torch.Tensor:
+    """``t`` flattened, or, beyond DUMP_SAMPLE elements, the same seeded sorted sample of it in every run."""
+    t = t.detach().reshape(-1)
+    if t.numel() <= DUMP_SAMPLE:
+        return t
+    idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), size=DUMP_SAMPLE))
+    return t[torch.from_numpy(idx).to(t.device)]
+
+
+def _dump_outputs(out_dir: str, arrays) -> None:
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy().reshape(-1))
 
 
 def _fedavg_timing(model, di, fedavg, comm, ncomm, k, sync):
@@ -657,6 +689,8 @@ def _bench_infer(args, model, it, di, comm, B, S):
     comm.barrier()
     sync()
     dt = comm.all_reduce_max(time.perf_counter() - t0)
+    if args.dump_outputs and di.is_main:
+        _dump_outputs(args.dump_outputs, {"probs": _sample(probs)})
     n = di.world_size
     per = args.steps / dt
     if di.is_main:

@@ -219,7 +219,7 @@ def _scaling(argv):
     results = []
     for n in (int(x) for x in ns.gpus.split(",")):
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", str(ns.steps),
-               "--warmup", str(ns.warmup)] + extra
+               "--warmup", str(ns.warmup), "--full"] + extra  # (--full: the FedAvg round times of the table)
         env = dict(os.environ)
         for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):  # bench.py launches its own ranks
             env.pop(k, None)

@@ -1,5 +1,5 @@
 """Per-round, per-client table of a multi-round virtual-client bench record
-(``bench.py --virtual-clients N --rounds R``: the ``per_round`` field of its JSON line).
+(``bench.py --full --virtual-clients N --rounds R``: the ``per_round`` field of its JSON line).
 
     python scripts/fed_rounds_report.py gpurun_out/r6fed/fedavg_8x3_default.json.log [title]
 """

@@ -5,7 +5,7 @@
 #
 # tasks (every GPU step under its own timeout, chained with &&; output under gpurun_out/<name>):
 #   tests   [pytest args]   the GPU suite (-m gpu), or the named test files / -k filters
-#   bench   [bench args]    bench.py (default --steps 50 --warmup 10), last JSON line kept
+#   bench   [bench args]    bench.py (default --full --steps 50 --warmup 10), last JSON line kept
 #   prof    [bench args]    rocprofv3 --kernel-trace --stats of the timed step -> kernel_stats.txt
 #   pmc                     PMC counter passes of the eager step (gfx950 slot limits) -> pmc_summary.txt
 #   record                  tests + bench + prof + the distillation (config 5) bench: the round record
@@ -21,7 +21,7 @@ tests() {
   local rc=$?; tail -6 "$O/tests.log"; return $rc
 }
 bench() {
-  local args=("$@"); [ ${#args[@]} -eq 0 ] && args=(--steps 50 --warmup 10)
+  local args=("$@"); [ ${#args[@]} -eq 0 ] && args=(--full --steps 50 --warmup 10)
   timeout -k 10 600 python bench.py "${args[@]}" > "$O/bench.log" 2>&1 && tail -1 "$O/bench.log" | cut -c1-400
 }
 prof() {
@@ -53,7 +53,7 @@ case "$task" in
   pmc) pmc ;;
   record)
     tests && bench && prof &&
-      timeout -k 10 600 python bench.py --steps 30 --warmup 5 --teacher --seq-len 256 --batch-size 64 \
+      timeout -k 10 600 python bench.py --full --steps 30 --warmup 5 --teacher --seq-len 256 --batch-size 64 \
         > "$O/kd.log" 2>&1 && tail -1 "$O/kd.log" | cut -c1-300 ;;
   run) timeout -k 10 600 "$@" > "$O/run.log" 2>&1; rc=$?; tail -30 "$O/run.log"; exit $rc ;;
   *) echo "usage: scripts/gpu.sh tests|bench|prof|pmc|record|run <name> [args]"; exit 2 ;;

@@ -8,7 +8,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_json_line():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--impl", "torch", "--layers", "1",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--impl", "torch", "--layers", "1",
                           "--steps", "2", "--warmup", "1", "--batch-size", "2", "--seq-len", "64"],
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -29,6 +29,48 @@ def test_bench_json_line():
     assert d["eval_rows"] == sum(c["test_rows"] for c in pc)
 
 
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """Without --full the run stops at its headline figure (no quality protocol, no FedAvg timing),
+    --steps is the number of timed steps, and --dump-outputs writes the last timed step's outputs
+    as float32 .npy files that a second run with the same arguments reproduces: the inputs are
+    seeded, so two runs differ only by the order of the threaded fp32 sums (observed 2e-7 relative;
+    bound: ~100 fp32 ulps)."""
+    import numpy as np
+    dumps = []
+    for name in ("a", "b"):
+        dumps.append(tmp_path / name)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--impl", "torch", "--layers", "1",
+                              "--steps", "3", "--warmup", "1", "--batch-size", "2", "--seq-len", "64",
+                              "--quality-rows", "600", "--dump-outputs", str(dumps[-1])],
+                             capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 3 and d["ms_per_step"] > 0
+        assert abs(d["value"] - 1000.0 / d["ms_per_step"]) <= 1e-3 * d["value"]
+        assert not any(k.startswith(("quality", "aggregated", "fedavg", "allreduce")) for k in d), sorted(d)
+    files = sorted(p.name for p in dumps[0].iterdir())
+    assert files == ["loss.npy", "mean_loss.npy", "params_sample.npy"]
+    total = 0
+    for f in files:
+        a, b = np.load(dumps[0] / f), np.load(dumps[1] / f)
+        assert a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all()
+        if f == "params_sample.npy":
+            # Adam moves a weight by about lr = 2e-5 a step whatever its gradient's size, so where the
+            # gradient is rounding noise the two runs may part by up to 2 lr per step (4 + 2 priming
+            # steps); that may happen to a few weights only
+            assert np.abs(a - b).max() <= 2 * 2e-5 * 6
+            assert np.mean(~np.isclose(a, b, rtol=1e-5, atol=1e-7)) < 1e-3
+        else:
+            np.testing.assert_allclose(a, b, rtol=1e-5, atol=1e-7)
+        total += a.nbytes
+    assert total <= 64 * 2 ** 20
+    assert np.load(dumps[0] / "params_sample.npy").std() > 0
+
+
 def test_bench_spawns_ranks_itself():
     """--gpus 2 without a torchrun environment: bench.py starts 2 ranks as a child
     torch.distributed.run, every rank checks WORLD_SIZE, rank 0 prints the one line with the
@@ -36,7 +78,7 @@ def test_bench_spawns_ranks_itself():
     env = dict(os.environ, FEDDDOS_BACKEND="gloo")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--impl", "torch",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--impl", "torch",
                           "--layers", "1", "--steps", "2", "--warmup", "1", "--batch-size", "2", "--seq-len", "64"],
                          capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -106,7 +148,7 @@ def test_bench_eight_clients_gloo():
     env = dict(os.environ, FEDDDOS_BACKEND="gloo", OMP_NUM_THREADS="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--impl", "torch",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--full", "--impl", "torch",
                           "--layers", "1", "--steps", "2", "--warmup", "1", "--batch-size", "2", "--seq-len", "64",
                           "--quality-rows", "1200"],
                          capture_output=True, text=True, timeout=900, env=env)

@@ -1,5 +1,5 @@
 """Parity with the model the reference actually runs: HF ``transformers.DistilBertModel``
-(/root/reference/client1.py:56,61-64) + Dropout(0.3) + Linear(768, 2).
+(reference client1.py:56,61-64) + Dropout(0.3) + Linear(768, 2).
 
 Our ``state_dict()`` (102 keys) loads strict into the HF module tree; in eval mode the
 pure-torch path (``impl="torch"``, the CPU execution path and the oracle every HIP kernel test
