@@ -18,6 +18,7 @@ namespace py { struct gil_scoped_release {}; }  // (no Python in the host-only b
 #include <hip/hip_runtime.h>
 #endif
 
+#include <cmath>
 #include <cstdint>
 #include <vector>
 
@@ -134,10 +135,13 @@ int fd_eval_metrics(const float* logits, const long long* labels, int B, double*
 int fd_adam(float* p, const float* g, float* m, float* v, void* shadow, long long n, const int* step, float lr,
             float b1, float b2, float eps, float wd, int decoupled, const unsigned char* touched,
             const unsigned char* now, long long skip_off, long long skip_rows, int row_len, const long long* runs,
-            int nruns, long long run_total4, hipStream_t st);
+            int nruns, long long run_total4, const float* run_wd, hipStream_t st);
 int fd_adam_rows(float* p, const float* g, float* m, float* v, void* shadow, int rows, int row_len, const int* step,
                  float lr, float b1, float b2, float eps, const unsigned char* ever, const unsigned char* now,
-                 hipStream_t st);
+                 float wd, int decoupled, hipStream_t st);
+int fd_adam_lazy_decay(float* p, void* shadow, int* done, const unsigned char* ever, int rows, int row_len,
+                       const int* step, int adj, float lr, float wd, const void* ids, int ids64, long long n,
+                       hipStream_t st);
 int fd_step(int* step, uint32_t* seed, hipStream_t st);
 int fd_scale_cast(float* p, void* shadow, long long n, float scale, hipStream_t st);
 int fd_axpby(float* dst, const float* x, const float* y, float a, float b, long long n, hipStream_t st);
@@ -348,6 +352,12 @@ int64_t gemm_dw2(const at::Tensor& A0, const at::Tensor& B0, const at::Tensor& C
   return splits;  // > 0: slabs left in `workspace` (problem 0 then 1) for splitk_reduce_batched
 }
 
+// A weight decay per parameter group: finite and non-negative.
+void need_decays(const std::vector<double>& wd, size_t n, const char* what) {
+  TORCH_CHECK(wd.size() == n, what, ": expected ", n, " weight decays, got ", wd.size());
+  for (double w : wd) TORCH_CHECK(std::isfinite(w) && w >= 0.0, what, ": a weight decay must be finite and >= 0");
+}
+
 // Every weight gradient of a backward in one launch (gemm.hip gemm_dw_batch_kernel):
 // Cs[i] (+)= As[i]^T Bs[i] (fp32), As[i] [K_i][M_i], Bs[i] [K_i][N_i] bf16 (K_i % 64 == 0).
 // adam: empty, or [p, m, v, shadow] per problem + the device step counter last (fused
@@ -356,7 +366,14 @@ void gemm_dw_batch(const std::vector<at::Tensor>& As, const std::vector<at::Tens
                    const std::vector<at::Tensor>& Cs, const std::vector<int64_t>& accumulate,
                    const std::vector<at::Tensor>& adam, const std::vector<double>& hp, int64_t cfg,
                    const std::vector<at::Tensor>& biases = {}, const std::vector<at::Tensor>& rest = {},
-                   const std::vector<int64_t>& rest_i = {}) {
+                   const std::vector<int64_t>& rest_i = {}, const std::vector<double>& decay = {},
+                   const std::vector<double>& bias_decay = {},
+                   const c10::optional<at::Tensor>& rest_wd = c10::nullopt,
+                   const std::vector<double>& rest_wd_host = {}, double word_wd = 0.0) {
+  // decay / bias_decay (with adam): per problem the weight decay of its matrix / of its bias
+  // (parameter groups; empty = hp's for all).  rest_wd: per-run weight decay of the rest's run
+  // table (device fp32 [nruns]) with the same values in rest_wd_host (checked here); word_wd: the
+  // word table's (non-zero only with decoupled decay -- its rows without state decay lazily).
   // biases: empty, or per problem an fp32 [M] producer-bias gradient (+)= column sums of A (an
   // empty tensor: none), accumulated like the problem's gradient
   // rest (with adam): the rest of the optimizer step in the same launch (FdAdamRest) -- [master,
@@ -405,10 +422,21 @@ void gemm_dw_batch(const std::vector<at::Tensor>& As, const std::vector<at::Tens
       TORCH_CHECK(!accumulate[i], "gemm_dw_batch: a fused Adam step cannot accumulate into a gradient");
       pr[i].p = ad[i].p; pr[i].m = ad[i].m; pr[i].v = ad[i].v; pr[i].sh = ad[i].sh;
     }
+    if (!decay.empty()) need_decays(decay, n, "gemm_dw_batch decay");
+    if (!bias_decay.empty()) need_decays(bias_decay, n, "gemm_dw_batch bias_decay");
+    for (size_t i = 0; i < n; ++i) {
+      pr[i].wd = decay.empty() ? ad[0].wd : (float)decay[i];
+      pr[i].bias_wd = bias_decay.empty() ? ad[0].wd : (float)bias_decay[i];
+    }
     step = ad[0].step;
     hyper[0] = ad[0].lr; hyper[1] = ad[0].b1; hyper[2] = ad[0].b2; hyper[3] = ad[0].eps; hyper[4] = ad[0].wd;
     hyper[5] = (float)ad[0].decoupled;
   }
+  TORCH_CHECK(!adam.empty() || (decay.empty() && bias_decay.empty()),
+              "gemm_dw_batch: weight decays need the fused Adam");
+  const bool has_rest_wd = rest_wd.has_value() && rest_wd->defined();
+  TORCH_CHECK(!rest.empty() || (!has_rest_wd && rest_wd_host.empty() && word_wd == 0.0),
+              "gemm_dw_batch: rest weight decays without the rest of the step");
   FdAdamRest rs{};
   if (!rest.empty()) {
     TORCH_CHECK(!adam.empty(), "gemm_dw_batch: the rest of the optimizer step needs the fused Adam");
@@ -426,6 +454,17 @@ void gemm_dw_batch(const std::vector<at::Tensor>& As, const std::vector<at::Tens
     rs.runs = rest[5].size(0) ? reinterpret_cast<const long long*>(rest[5].data_ptr()) : nullptr;
     rs.nruns = (int)rest[5].size(0);
     rs.n4 = n4;
+    TORCH_CHECK(has_rest_wd || rest_wd_host.empty(), "gemm_dw_batch: rest_wd_host without rest_wd");
+    if (has_rest_wd) {
+      need(*rest_wd, at::kFloat, "rest_wd");
+      TORCH_CHECK(rs.nruns > 0 && rest_wd->numel() == rs.nruns, "gemm_dw_batch: one weight decay per run");
+      need_decays(rest_wd_host, (size_t)rs.nruns, "gemm_dw_batch rest_wd");
+      rs.run_wd = rest_wd->data_ptr<float>();
+    }
+    TORCH_CHECK(std::isfinite(word_wd) && word_wd >= 0.0, "gemm_dw_batch: word_wd must be finite and >= 0");
+    TORCH_CHECK(word_wd == 0.0 || (rest.size() == 8 && hp[5] != 0.0),
+                "gemm_dw_batch: a decaying sparse word table needs its row flags and decoupled decay");
+    rs.wwd = (float)word_wd;
     if (rest.size() == 8) {
       need(rest[6], at::kByte, "rest ever");
       need(rest[7], at::kByte, "rest now");
@@ -1513,7 +1552,11 @@ void adam(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, const a
           const c10::optional<at::Tensor>& shadow, const at::Tensor& step, double lr, double b1, double b2, double eps,
           double wd, bool decoupled, const c10::optional<at::Tensor>& touched, const c10::optional<at::Tensor>& now,
           int64_t skip_off, int64_t skip_rows, int64_t row_len, const c10::optional<at::Tensor>& runs,
-          int64_t run_total4, int64_t run_end4) {
+          int64_t run_total4, int64_t run_end4, const c10::optional<at::Tensor>& run_wd = c10::nullopt,
+          const std::vector<double>& run_wd_host = {}) {
+  // run_wd: per-run weight decay (device fp32 [nruns], parameter groups) with the same values in
+  // run_wd_host, checked here; none = wd for every run
+  TORCH_CHECK(std::isfinite(wd) && wd >= 0.0, "adam: weight decay must be finite and >= 0");
   need_opt(touched, at::kByte, "touched");
   need_opt(now, at::kByte, "now");
   if (touched.has_value() && touched->defined()) {
@@ -1544,18 +1587,34 @@ void adam(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, const a
     rp = reinterpret_cast<const long long*>(runs->data_ptr<int64_t>());
     total4 = run_total4;
   }
+  const float* rwd = nullptr;
+  if (run_wd.has_value() && run_wd->defined()) {
+    need(*run_wd, at::kFloat, "adam run_wd");
+    TORCH_CHECK(rp != nullptr && run_wd->numel() == nruns, "adam: one weight decay per run");
+    TORCH_CHECK(!(touched.has_value() && touched->defined()), "adam: per-run decay takes no row flags");
+    need_decays(run_wd_host, (size_t)nruns, "adam run_wd");
+    rwd = run_wd->data_ptr<float>();
+  } else {
+    TORCH_CHECK(run_wd_host.empty(), "adam: run_wd_host without run_wd");
+  }
+  if (touched.has_value() && touched->defined())
+    TORCH_CHECK(wd == 0.0 || decoupled, "adam: row flags with weight decay need decoupled decay");
   check_rc(fd_adam(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
                    ptr<void>(shadow), n, step.data_ptr<int>(), (float)lr, (float)b1, (float)b2, (float)eps, (float)wd,
                    decoupled ? 1 : 0, ptr<const unsigned char>(touched), ptr<const unsigned char>(now), skip_off,
-                   skip_rows, (int)row_len, rp, nruns, total4, stream()),
+                   skip_rows, (int)row_len, rp, nruns, total4, rwd, stream()),
            "adam");
 }
 
-// Adam (weight decay 0) over the rows of a [rows][row_len] table whose `ever` flag is set
-// (gradient taken as 0 unless now[row]); p, g, m, v (and shadow) are that table's views.
+// Adam over the rows of a [rows][row_len] table whose `ever` flag is set (gradient taken as 0
+// unless now[row]); p, g, m, v (and shadow) are that table's views.  wd != 0 needs decoupled
+// decay: the rows without state are decayed lazily (adam_lazy_decay).
 void adam_rows(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, const at::Tensor& v,
                const c10::optional<at::Tensor>& shadow, const at::Tensor& step, double lr, double b1, double b2,
-               double eps, const at::Tensor& ever, const c10::optional<at::Tensor>& now, int64_t row_len) {
+               double eps, const at::Tensor& ever, const c10::optional<at::Tensor>& now, int64_t row_len,
+               double wd = 0.0, bool decoupled = false) {
+  TORCH_CHECK(std::isfinite(wd) && wd >= 0.0, "adam_rows: weight decay must be finite and >= 0");
+  TORCH_CHECK(wd == 0.0 || decoupled, "adam_rows: weight decay needs decoupled decay");
   need(p, at::kFloat, "p");
   need(g, at::kFloat, "g");
   need(m, at::kFloat, "m");
@@ -1574,8 +1633,46 @@ void adam_rows(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, co
   check_rc(fd_adam_rows(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
                         ptr<void>(shadow), (int)rows, (int)row_len, step.data_ptr<int>(), (float)lr, (float)b1,
                         (float)b2, (float)eps, ever.data_ptr<unsigned char>(), ptr<const unsigned char>(now),
-                        stream()),
+                        (float)wd, decoupled ? 1 : 0, stream()),
            "adam_rows");
+}
+
+// The decoupled decay owed to the rows of a [rows][row_len] table that have no Adam state
+// (ever[row] == 0): done[row] (int32) counts the steps already applied; every row named by ids
+// (int32 / int64, any shape; none = every row) is brought up to step[0] - adj steps, master and
+// shadow.  Ids outside the table are ignored by the kernel.
+void adam_lazy_decay(const at::Tensor& p, const c10::optional<at::Tensor>& shadow, const at::Tensor& done,
+                     const at::Tensor& ever, const at::Tensor& step, int64_t adj, double lr, double wd,
+                     int64_t row_len, const c10::optional<at::Tensor>& ids) {
+  need(p, at::kFloat, "p");
+  need_opt(shadow, at::kBFloat16, "shadow");
+  need(done, at::kInt, "done");
+  need(ever, at::kByte, "ever");
+  need(step, at::kInt, "step");
+  TORCH_CHECK(std::isfinite(wd) && wd >= 0.0 && std::isfinite(lr), "adam_lazy_decay: lr / weight decay");
+  TORCH_CHECK(adj == 0 || adj == 1, "adam_lazy_decay: adj is 0 or 1");
+  const int64_t n = p.numel();
+  TORCH_CHECK(row_len > 0 && row_len % 4 == 0 && n > 0 && n % row_len == 0,
+              "adam_lazy_decay: rows of row_len (multiple of 4)");
+  const int64_t rows = n / row_len;
+  TORCH_CHECK(rows < (int64_t(1) << 31), "adam_lazy_decay: too many rows");
+  if (shadow.has_value() && shadow->defined()) TORCH_CHECK(shadow->numel() == n, "adam_lazy_decay: shadow size");
+  TORCH_CHECK(done.numel() >= rows && ever.numel() >= rows && step.numel() >= 1, "adam_lazy_decay: flag sizes");
+  const void* idp = nullptr;
+  int ids64 = 0;
+  int64_t nids = 0;
+  if (ids.has_value() && ids->defined()) {
+    TORCH_CHECK(ids->scalar_type() == at::kLong || ids->scalar_type() == at::kInt, "adam_lazy_decay: ids int32 / int64");
+    need(*ids, ids->scalar_type(), "ids");
+    nids = ids->numel();
+    TORCH_CHECK(nids > 0 && nids <= (int64_t(1) << 30), "adam_lazy_decay: ids count");
+    idp = ids->data_ptr();
+    ids64 = ids->scalar_type() == at::kLong;
+  }
+  check_rc(fd_adam_lazy_decay(p.data_ptr<float>(), ptr<void>(shadow), done.data_ptr<int>(),
+                              ever.data_ptr<unsigned char>(), (int)rows, (int)row_len, step.data_ptr<int>(), (int)adj,
+                              (float)lr, (float)wd, idp, ids64, nids, stream()),
+           "adam_lazy_decay");
 }
 
 void step_inc(const c10::optional<at::Tensor>& step, const c10::optional<at::Tensor>& seed) {
@@ -1625,7 +1722,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("head_dx") = py::none(), py::arg("head_tlogits") = py::none(), py::arg("head_own") = py::none());
   m.def("gemm_dw2", &gemm_dw2);
   m.def("gemm_dw", &gemm_dw);
-  m.def("adam_rows", &adam_rows);
+  m.def("adam_rows", &adam_rows, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("shadow"),
+        py::arg("step"), py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("ever"), py::arg("now"),
+        py::arg("row_len"), py::arg("wd") = 0.0, py::arg("decoupled") = false);
+  m.def("adam_lazy_decay", &adam_lazy_decay, py::arg("p"), py::arg("shadow"), py::arg("done"), py::arg("ever"),
+        py::arg("step"), py::arg("adj"), py::arg("lr"), py::arg("wd"), py::arg("row_len"),
+        py::arg("ids") = py::none());
   m.def("gemm_ln", &gemm_ln, py::arg("bwd"), py::arg("A"), py::arg("Bt"), py::arg("C"), py::arg("bias"),
         py::arg("res"), py::arg("gamma"), py::arg("beta"), py::arg("mean"), py::arg("rstd"), py::arg("z"),
         py::arg("dx"), py::arg("colpart"), py::arg("stats"), py::arg("cnt"), py::arg("err"), py::arg("eps"),
@@ -1635,7 +1737,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_dw_batch", &gemm_dw_batch, py::arg("As"), py::arg("Bs"), py::arg("Cs"), py::arg("accumulate"),
         py::arg("adam"), py::arg("hp"), py::arg("cfg") = -1,
         py::arg("biases") = std::vector<at::Tensor>{}, py::arg("rest") = std::vector<at::Tensor>{},
-        py::arg("rest_i") = std::vector<int64_t>{});
+        py::arg("rest_i") = std::vector<int64_t>{}, py::arg("decay") = std::vector<double>{},
+        py::arg("bias_decay") = std::vector<double>{}, py::arg("rest_wd") = py::none(),
+        py::arg("rest_wd_host") = std::vector<double>{}, py::arg("word_wd") = 0.0);
   m.def("gemm_colsum", &gemm_colsum, py::arg("epi"), py::arg("A"), py::arg("B"), py::arg("C"), py::arg("aux"),
         py::arg("res"), py::arg("colsum"), py::arg("aux_out") = py::none(), py::arg("kind") = 0,
         py::arg("prefetch") = py::none());

@@ -118,6 +118,9 @@ int fd_gemm_dw_batch(int n, const FdDwProb* probs, int K, const int* step, const
   if (rest) {
     if (!hyper || !step) hc::violations.push_back("dw_batch rest without the fused Adam");
     if (rest->runs) hc::span(rest->runs, (long long)rest->nruns * 3 * 8, "dw_batch rest runs");
+    if (rest->run_wd) hc::span(rest->run_wd, (long long)rest->nruns * 4, "dw_batch rest run decays");
+    if (rest->wwd != 0.f && (!rest->ever || !hyper || hyper[5] == 0.f))
+      hc::violations.push_back("dw_batch: a decaying sparse word table without flags / decoupled decay");
     if (rest->ever) {
       hc::span(rest->ever, rest->wrows, "dw_batch rest ever");
       hc::span(rest->now, rest->wrows, "dw_batch rest now");
@@ -140,6 +143,7 @@ int fd_gemm_dw_batch(int n, const FdDwProb* probs, int K, const int* step, const
       hc::opt_span(q.sh, mn * 2, "dw_batch adam shadow");
       hc::span(step, 4, "dw_batch step");
       if (!hyper) hc::violations.push_back("dw_batch: fused Adam without hyper-parameters");
+      if (!(q.wd >= 0.f) || !(q.bias_wd >= 0.f)) hc::violations.push_back("dw_batch: negative / NaN weight decay");
     } else {
       hc::span(q.C, mn * 4, "dw_batch C");
     }
@@ -148,8 +152,10 @@ int fd_gemm_dw_batch(int n, const FdDwProb* probs, int K, const int* step, const
   return 0;
 }
 int fd_adam_rows(float* p, const float* g, float* m, float* v, void* shadow, int rows, int row_len, const int* step,
-                 float, float, float, float, const unsigned char* ever, const unsigned char* now, hipStream_t) {
+                 float, float, float, float, const unsigned char* ever, const unsigned char* now, float wd,
+                 int decoupled, hipStream_t) {
   ++hc::calls;
+  if (wd != 0.f && !decoupled) hc::violations.push_back("adam_rows: coupled weight decay on flagged rows");
   const long long n = (long long)rows * row_len;
   hc::span(p, n * 4, "adam_rows p");
   hc::span(g, n * 4, "adam_rows g");
@@ -159,6 +165,20 @@ int fd_adam_rows(float* p, const float* g, float* m, float* v, void* shadow, int
   hc::span(step, 4, "adam_rows step");
   hc::span(ever, rows, "adam_rows ever");
   hc::opt_span(now, rows, "adam_rows now");
+  return 0;
+}
+int fd_adam_lazy_decay(float* p, void* shadow, int* done, const unsigned char* ever, int rows, int row_len,
+                       const int* step, int adj, float, float wd, const void* ids, int ids64, long long n,
+                       hipStream_t) {
+  ++hc::calls;
+  const long long tot = (long long)rows * row_len;
+  hc::span(p, tot * 4, "lazy decay p");
+  hc::opt_span(shadow, tot * 2, "lazy decay shadow");
+  hc::span(done, (long long)rows * 4, "lazy decay done");
+  hc::span(ever, rows, "lazy decay ever");
+  hc::span(step, 4, "lazy decay step");
+  if (ids) hc::span(ids, n * (ids64 ? 8 : 4), "lazy decay ids");
+  if (adj < 0 || adj > 1 || !(wd >= 0.f)) hc::violations.push_back("lazy decay: adj / weight decay");
   return 0;
 }
 int fd_gemm_splitk(int epi, const void* A, const void* Bt, int M, int N, int K, float* workspace,
@@ -565,8 +585,13 @@ int fd_eval_metrics(const float*, const long long*, int, double*, long long*, fl
 }
 int fd_adam(float* p, const float* g, float* m, float* v, void* shadow, long long n, const int* step, float, float,
             float, float, float, int, const unsigned char* touched, const unsigned char* now, long long skip_off,
-            long long skip_rows, int row_len, const long long* runs, int nruns, long long run_total4, hipStream_t) {
+            long long skip_rows, int row_len, const long long* runs, int nruns, long long run_total4,
+            const float* run_wd, hipStream_t) {
   ++hc::calls;
+  if (run_wd) {
+    if (!runs) hc::violations.push_back("adam: run decays without a run table");
+    hc::span(run_wd, (long long)nruns * 4, "adam run decays");
+  }
   hc::span(p, n * 4, "adam p");
   hc::span(g, n * 4, "adam g");
   hc::span(m, n * 4, "adam m");
@@ -708,6 +733,42 @@ int main() {
     expect_ok("dw_batch", [&] { gemm_dw_batch(As, Bs, Cs, acc, {}, {}, -1); });
     expect_ok("dw_batch adam", [&] { gemm_dw_batch(As, Bs, Cs, acc, st, hp, -1); });
     expect_reject("dw_batch adam+accumulate", [&] { gemm_dw_batch(As, Bs, Cs, acc1, st, hp, -1); });
+    // parameter groups: a weight decay per problem (and per in-launch bias)
+    const std::vector<double> hpw = {2e-5, 0.9, 0.999, 1e-8, 0.01, 1.0};
+    expect_ok("dw_batch decays", [&] { gemm_dw_batch(As, Bs, Cs, acc, st, hpw, -1, {}, {}, {}, {0.01, 0.0, 0.01, 0.0}); });
+    expect_reject("dw_batch decays length", [&] { gemm_dw_batch(As, Bs, Cs, acc, st, hpw, -1, {}, {}, {}, {0.01, 0.0}); });
+    expect_reject("dw_batch decay negative", [&] {
+      gemm_dw_batch(As, Bs, Cs, acc, st, hpw, -1, {}, {}, {}, {0.01, 0.0, -1.0, 0.0}); });
+    expect_reject("dw_batch decay inf", [&] {
+      gemm_dw_batch(As, Bs, Cs, acc, st, hpw, -1, {}, {}, {}, {0.01, 0.0, INFINITY, 0.0}); });
+    expect_reject("dw_batch bias decays length", [&] {
+      gemm_dw_batch(As, Bs, Cs, acc, st, hpw, -1, {}, {}, {}, {}, {0.0}); });
+    expect_reject("dw_batch decays without adam", [&] {
+      gemm_dw_batch(As, Bs, Cs, acc, {}, {}, -1, {}, {}, {}, {0.01, 0.0, 0.01, 0.0}); });
+    {  // the rest of the step in the launch: per-run decays and the word table's decay
+      const int64_t an = 64 * 64 + 1024;
+      std::vector<at::Tensor> rest = {T_({an}, f32), T_({an}, f32), T_({an}, f32), T_({an}, f32), T_({an}, bf),
+                                      T_({2, 3}, i64), T_({64}, at::kByte), T_({64}, at::kByte)};
+      auto rp = rest[5].data_ptr<int64_t>();
+      rp[0] = 1024; rp[1] = 128; rp[2] = 0; rp[3] = 1152; rp[4] = 128; rp[5] = 128;
+      const std::vector<int64_t> ri = {256, 0, 64, 64};
+      const c10::optional<at::Tensor> rw = T_({2}, f32), rw1 = T_({1}, f32);
+      expect_ok("dw_batch rest", [&] { gemm_dw_batch(As, Bs, Cs, acc, st, hpw, -1, {}, rest, ri); });
+      expect_ok("dw_batch rest decays", [&] {
+        gemm_dw_batch(As, Bs, Cs, acc, st, hpw, -1, {}, rest, ri, {}, {}, rw, {0.01, 0.0}, 0.01); });
+      expect_reject("dw_batch rest decays length", [&] {
+        gemm_dw_batch(As, Bs, Cs, acc, st, hpw, -1, {}, rest, ri, {}, {}, rw1, {0.01}, 0.0); });
+      expect_reject("dw_batch rest decays host", [&] {
+        gemm_dw_batch(As, Bs, Cs, acc, st, hpw, -1, {}, rest, ri, {}, {}, rw, {0.01}, 0.0); });
+      expect_reject("dw_batch rest decay negative", [&] {
+        gemm_dw_batch(As, Bs, Cs, acc, st, hpw, -1, {}, rest, ri, {}, {}, rw, {0.01, -0.5}, 0.0); });
+      expect_reject("dw_batch word decay coupled", [&] {
+        gemm_dw_batch(As, Bs, Cs, acc, st, {2e-5, 0.9, 0.999, 1e-8, 0.01, 0.0}, -1, {}, rest, ri, {}, {}, none, {}, 0.01); });
+      expect_reject("dw_batch word decay negative", [&] {
+        gemm_dw_batch(As, Bs, Cs, acc, st, hpw, -1, {}, rest, ri, {}, {}, none, {}, -0.01); });
+      expect_reject("dw_batch rest decays without rest", [&] {
+        gemm_dw_batch(As, Bs, Cs, acc, st, hpw, -1, {}, {}, {}, {}, {}, rw, {0.01, 0.0}, 0.0); });
+    }
     auto Bbad = Bs;
     Bbad[2] = T_({2000, 768}, bf);
     expect_reject("dw_batch K mismatch", [&] { gemm_dw_batch(As, Bbad, Cs, acc, {}, {}, -1); });
@@ -901,6 +962,42 @@ int main() {
     expect_reject("adam rows flags", [&] { adam_rows(p, g, m, v, sh, step, 2e-5, 0.9, 0.999, 1e-8, ever_small, now,
                                                      64); });
     expect_reject("adam rows row_len", [&] { adam_rows(p, g, m, v, sh, step, 2e-5, 0.9, 0.999, 1e-8, ever, now, 6); });
+    // parameter groups: a weight decay per run
+    const c10::optional<at::Tensor> rwd = T_({2}, f32), rwd3 = T_({3}, f32);
+    expect_ok("adam run decays", [&] { adam(p, g, m, v, sh, step, 2e-5, 0.9, 0.999, 1e-8, 0.01, true, none, none, 0, 0,
+                                            4, runs, 320, 768, rwd, {0.01, 0.0}); });
+    expect_reject("adam run decays length", [&] { adam(p, g, m, v, sh, step, 2e-5, 0.9, 0.999, 1e-8, 0.01, true, none,
+                                                       none, 0, 0, 4, runs, 320, 768, rwd3, {0.01, 0.0, 0.0}); });
+    expect_reject("adam run decays host length", [&] { adam(p, g, m, v, sh, step, 2e-5, 0.9, 0.999, 1e-8, 0.01, true,
+                                                            none, none, 0, 0, 4, runs, 320, 768, rwd, {0.01}); });
+    expect_reject("adam run decay negative", [&] { adam(p, g, m, v, sh, step, 2e-5, 0.9, 0.999, 1e-8, 0.01, true, none,
+                                                        none, 0, 0, 4, runs, 320, 768, rwd, {0.01, -0.01}); });
+    expect_reject("adam run decay NaN", [&] { adam(p, g, m, v, sh, step, 2e-5, 0.9, 0.999, 1e-8, 0.01, true, none, none,
+                                                   0, 0, 4, runs, 320, 768, rwd, {0.01, std::nan("")}); });
+    expect_reject("adam run decays without runs", [&] { adam(p, g, m, v, sh, step, 2e-5, 0.9, 0.999, 1e-8, 0.01, true,
+                                                             none, none, 0, 0, 4, none, 0, 0, rwd, {0.01, 0.0}); });
+    expect_reject("adam weight decay negative", [&] { adam(p, g, m, v, sh, step, 2e-5, 0.9, 0.999, 1e-8, -0.01, true,
+                                                           none, none, 0, 0, 4, none, 0, 0); });
+    // flagged rows under weight decay: decoupled only (the other rows decay lazily)
+    expect_ok("adam rows decoupled decay", [&] { adam_rows(p, g, m, v, sh, step, 2e-5, 0.9, 0.999, 1e-8, ever, now, 64,
+                                                           0.01, true); });
+    expect_reject("adam rows coupled decay", [&] { adam_rows(p, g, m, v, sh, step, 2e-5, 0.9, 0.999, 1e-8, ever, now,
+                                                             64, 0.01, false); });
+    expect_ok("adam flags decoupled decay", [&] { adam(p, g, m, v, sh, step, 2e-5, 0.9, 0.999, 1e-8, 0.01, true, ever,
+                                                       now, 0, 64, 64, none, 0, 0); });
+    expect_reject("adam flags coupled decay", [&] { adam(p, g, m, v, sh, step, 2e-5, 0.9, 0.999, 1e-8, 0.01, false, ever,
+                                                         now, 0, 64, 64, none, 0, 0); });
+    // the lazy decay of rows without state (all rows, or the rows of a batch's ids)
+    auto done = T_({64}, i32), done_small = T_({10}, i32), ids = T_({4, 8}, i64), ids32 = T_({32}, i32);
+    expect_ok("lazy decay all rows", [&] { adam_lazy_decay(p, sh, done, ever, step, 0, 2e-5, 0.01, 64, none); });
+    expect_ok("lazy decay ids", [&] { adam_lazy_decay(p, sh, done, ever, step, 1, 2e-5, 0.01, 64, ids); });
+    expect_ok("lazy decay int32 ids", [&] { adam_lazy_decay(p, none, done, ever, step, 0, 2e-5, 0.01, 64, ids32); });
+    expect_reject("lazy decay counters", [&] { adam_lazy_decay(p, sh, done_small, ever, step, 0, 2e-5, 0.01, 64, none); });
+    expect_reject("lazy decay flags", [&] { adam_lazy_decay(p, sh, done, ever_small, step, 0, 2e-5, 0.01, 64, none); });
+    expect_reject("lazy decay row_len", [&] { adam_lazy_decay(p, sh, done, ever, step, 0, 2e-5, 0.01, 6, none); });
+    expect_reject("lazy decay adj", [&] { adam_lazy_decay(p, sh, done, ever, step, 2, 2e-5, 0.01, 64, none); });
+    expect_reject("lazy decay negative", [&] { adam_lazy_decay(p, sh, done, ever, step, 0, 2e-5, -0.01, 64, none); });
+    expect_reject("lazy decay ids dtype", [&] { adam_lazy_decay(p, sh, done, ever, step, 0, 2e-5, 0.01, 64, g); });
   }
   // ---- embedding backward (work = pieces + LayerNorm partials)
   {

@@ -21,6 +21,13 @@ DEV void adam_elem(float lr, float b1, float b2, float eps, float wd, int decoup
   p -= step_size * m / denom;
 }
 
+// The whole step of an element with m = v = g = 0 under decoupled decay (adam_elem's first line:
+// the same fp32 expression, contraction off -- its Adam term is exactly 0).
+DEV void adam_decay(float lr, float wd, float& p) {
+#pragma clang fp contract(off)
+  p *= 1.f - lr * wd;
+}
+
 DEV void adam_bias_corr(const int* step, float lr, float b1, float b2, float& step_size, float& inv_sqrt_bc2) {
   const int t = step[0];
   const float bc1 = 1.f - powf(b1, (float)t);
@@ -48,16 +55,21 @@ struct AdamArgs {
   // applied Adam to the encoder matrices in their epilogues: one launch covers the rest.
   const long long* runs;
   int nruns;
+  // Per-run weight decay, parallel to the run table (nullable = wd for every run): parameter
+  // groups -- biases and LayerNorm affines usually decay by 0 (engine/optim.py no_decay).
+  const float* run_wd;
 };
 
 // virtual index -> arena float4 index through the run table (binary search on the prefix)
-DEV long long run_index(const long long* runs, int nruns, long long i) {
+// (run: the run's number, for the per-run decay)
+DEV long long run_index(const long long* runs, int nruns, long long i, int& run) {
   int lo = 0, hi = nruns - 1;
   while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
     if (runs[3 * mid + 2] <= i) lo = mid;
     else hi = mid - 1;
   }
+  run = lo;
   return runs[3 * lo] + (i - runs[3 * lo + 2]);
 }
 
@@ -72,12 +84,16 @@ DEV void st_nt(float4* p, float4 v) {
   __builtin_nontemporal_store(f32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4*>(p));
 }
 
-// The Adam update of 4 elements (adam_elem each).
-DEV void adam_math4(const AdamArgs& a, float (&pp)[4], const float (&gg)[4], float (&mm)[4], float (&vv)[4],
-                    float step_size, float inv_sqrt_bc2) {
+// The Adam update of 4 elements (adam_elem each) with weight decay wd.
+DEV void adam_math4(const AdamArgs& a, float wd, float (&pp)[4], const float (&gg)[4], float (&mm)[4],
+                    float (&vv)[4], float step_size, float inv_sqrt_bc2) {
 #pragma unroll
   for (int e = 0; e < 4; ++e)
-    adam_elem(a.lr, a.b1, a.b2, a.eps, a.wd, a.decoupled, pp[e], gg[e], mm[e], vv[e], step_size, inv_sqrt_bc2);
+    adam_elem(a.lr, a.b1, a.b2, a.eps, wd, a.decoupled, pp[e], gg[e], mm[e], vv[e], step_size, inv_sqrt_bc2);
+}
+DEV void adam_math4(const AdamArgs& a, float (&pp)[4], const float (&gg)[4], float (&mm)[4], float (&vv)[4],
+                    float step_size, float inv_sqrt_bc2) {
+  adam_math4(a, a.wd, pp, gg, mm, vv, step_size, inv_sqrt_bc2);
 }
 
 // One flagged row of a [rows][row4] float4 table starting at float4 base4 (one wave; gradient 0
@@ -105,7 +121,9 @@ DEV void adam_row(const AdamArgs& a, long long base4, int row, int row4, int lan
 // One float4 of a flat / run-table Adam (adam_kernel's body; NT: nontemporal g / m / v, NTP: also p).
 template <bool NT, bool NTP>
 DEV void adam_flat4(const AdamArgs& a, long long vi, float step_size, float inv_sqrt_bc2) {
-  const long long i = a.runs ? run_index(a.runs, a.nruns, vi) : vi;
+  int run = 0;
+  const long long i = a.runs ? run_index(a.runs, a.nruns, vi, run) : vi;
+  const float wd = a.run_wd ? a.run_wd[run] : a.wd;
   // Rows never touched since the moments were reset have m = v = g = 0: their
   // Adam update is exactly zero, so skip all their traffic (wd == 0 only).
   bool gvalid = true;
@@ -127,7 +145,7 @@ DEV void adam_flat4(const AdamArgs& a, long long vi, float step_size, float inv_
   }
   float pp[4] = {p.x, p.y, p.z, p.w}, gg[4] = {g.x, g.y, g.z, g.w};
   float mm[4] = {m.x, m.y, m.z, m.w}, vv[4] = {v.x, v.y, v.z, v.w};
-  adam_math4(a, pp, gg, mm, vv, step_size, inv_sqrt_bc2);
+  adam_math4(a, wd, pp, gg, mm, vv, step_size, inv_sqrt_bc2);
   if constexpr (NTP)
     st_nt(reinterpret_cast<float4*>(a.p) + i, make_float4(pp[0], pp[1], pp[2], pp[3]));
   else

@@ -33,10 +33,12 @@ struct FdDwProb {
   int tile0;          // filled by the launcher
   int accumulate;
   int K;              // rows of A and B (0: the launch's K)
+  float wd;           // this matrix's weight decay (its parameter group's; with p)
   // nullable: also bias[m] (+)= sum_k A[k][m] -- the producer's bias gradient (the qkv bias: A is
   // dqkv), summed by the tiles of the first column block while their K loops read A anyway
   float* bias;
   int half;           // filled by the launcher: 1 = tiled 256 x 128 (the mixed schedule's tail class)
+  float bias_wd;      // the bias's weight decay, when the launch's tiles also apply its Adam step
 };
 
 // The rest of the optimizer step, run by extra blocks of the all-layer dW launch beside its last
@@ -44,8 +46,11 @@ struct FdDwProb {
 // epilogues do not update.  p / g / m / v / sh are the whole arenas; runs: the run table over them
 // ([start4, count4, prefix4] rows, head_optim.hip AdamArgs) of everything but the word table, n4
 // its float4 total; the word table ([wrows][wrow4 float4] at element woff) by its row flags
-// (ever: has Adam state, now: has a gradient this step; weight decay 0).  The qkv bias, whose
-// gradient the launch itself sums, is updated by the tiles that sum it (GemmParams::acol_*).
+// (ever: has Adam state, now: has a gradient this step; weight decay wwd -- non-zero only with
+// decoupled decay, the rows without state then decay lazily: head_optim.hip
+// adam_lazy_decay_kernel).  run_wd: per-run weight decay parallel to runs (nullable = the
+// launch's).  The qkv bias, whose gradient the launch itself sums, is updated by the tiles that
+// sum it (GemmParams::acol_*) with its own decay (FdDwProb::bias_wd).
 struct FdAdamRest {
   float* p;
   const float* g;
@@ -61,6 +66,8 @@ struct FdAdamRest {
   const unsigned char* now;
   int flat_blocks, row_blocks;  // filled by the launcher
   int first;                    // the rest blocks lead the grid (else they follow the tiles)
+  const float* run_wd;
+  float wwd;
 };
 
 #define FD_LN_XSITES 128

@@ -92,6 +92,7 @@ struct GemmParams {
   float* acol_m;
   float* acol_v;
   uint16_t* acol_sh;
+  float acol_wd;         // the bias's weight decay (its parameter group's, not the matrix's)
   int ln2_half;          // EPI_LN2*: this block's K half and the 64-column half of the tile it finishes
 };
 
@@ -1268,7 +1269,7 @@ DEV void gemm_tile_at(const GemmParams& p, int tm, int tn, char* smem) {
             float ss, inv;
             adam_bias_corr(p.adam.step, p.adam.lr, p.adam.b1, p.adam.b2, ss, inv);
             float pb = p.acol_p[m], mb = p.acol_m[m], vb = p.acol_v[m];
-            adam_elem(p.adam.lr, p.adam.b1, p.adam.b2, p.adam.eps, p.adam.wd, p.adam.decoupled, pb, s, mb, vb, ss,
+            adam_elem(p.adam.lr, p.adam.b1, p.adam.b2, p.adam.eps, p.acol_wd, p.adam.decoupled, pb, s, mb, vb, ss,
                       inv);
             p.acol_p[m] = pb;
             p.acol_m[m] = mb;
@@ -1817,12 +1818,13 @@ DEV void dwb_tile(const DwBatch& bt, int lid, char* smem) {
   p.acol = q.bias;
   if (q.p) {
     p.adam.p = q.p; p.adam.m = q.m; p.adam.v = q.v; p.adam.sh = q.sh; p.adam.step = bt.step;
-    p.adam.lr = bt.lr; p.adam.b1 = bt.b1; p.adam.b2 = bt.b2; p.adam.eps = bt.eps; p.adam.wd = bt.wd;
+    p.adam.lr = bt.lr; p.adam.b1 = bt.b1; p.adam.b2 = bt.b2; p.adam.eps = bt.eps; p.adam.wd = q.wd;
     p.adam.decoupled = bt.decoupled;
     if (q.bias && bt.rest.p) {  // the qkv bias's state lies at its gradient's arena offset
       const ptrdiff_t off = q.bias - bt.rest.g;
       p.acol_p = bt.rest.p + off; p.acol_m = bt.rest.m + off; p.acol_v = bt.rest.v + off;
       p.acol_sh = bt.rest.sh ? bt.rest.sh + off : nullptr;
+      p.acol_wd = q.bias_wd;
     }
   }
   if constexpr (MIX) {
@@ -1864,6 +1866,7 @@ DEV void dwb_rest(const DwBatch& bt, int rb, char* smem) {
     a.p = r.p; a.g = r.g; a.m = r.m; a.v = r.v; a.shadow = reinterpret_cast<bf16_t*>(r.sh);
     a.wd = bt.wd; a.decoupled = bt.decoupled;
     a.runs = r.runs; a.nruns = r.nruns; a.n4 = r.n4;
+    a.run_wd = r.run_wd;
     // adam_flat4's element body (the same arithmetic, bitwise), U float4 per thread at once: the
     // run lookups binary-search an LDS copy of the run table, and every load of the U elements is
     // issued before their stores (in turn each lookup chain and each load would wait for the
@@ -1878,11 +1881,14 @@ DEV void dwb_rest(const DwBatch& bt, int rb, char* smem) {
     const long long stride = (long long)r.flat_blocks * NT;
     for (long long v0 = (long long)rb * NT + threadIdx.x; v0 < r.n4; v0 += U * stride) {
       long long idx[U];
+      float wd[U];
       float4 p4[U], g4[U], m4[U], v4[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const long long vi = min(v0 + u * stride, r.n4 - 1);
-        idx[u] = a.runs ? run_index(a.runs, a.nruns, vi) : vi;
+        int run = 0;
+        idx[u] = a.runs ? run_index(a.runs, a.nruns, vi, run) : vi;
+        wd[u] = a.run_wd ? a.run_wd[run] : a.wd;
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -1897,7 +1903,7 @@ DEV void dwb_rest(const DwBatch& bt, int rb, char* smem) {
         const long long i = idx[u];
         float pp[4] = {p4[u].x, p4[u].y, p4[u].z, p4[u].w}, gg[4] = {g4[u].x, g4[u].y, g4[u].z, g4[u].w};
         float mm[4] = {m4[u].x, m4[u].y, m4[u].z, m4[u].w}, vv[4] = {v4[u].x, v4[u].y, v4[u].z, v4[u].w};
-        adam_math4(a, pp, gg, mm, vv, ss, inv);
+        adam_math4(a, wd[u], pp, gg, mm, vv, ss, inv);
         st_nt(reinterpret_cast<float4*>(a.p) + i, make_float4(pp[0], pp[1], pp[2], pp[3]));
         st_nt(reinterpret_cast<float4*>(a.m) + i, make_float4(mm[0], mm[1], mm[2], mm[3]));
         st_nt(reinterpret_cast<float4*>(a.v) + i, make_float4(vv[0], vv[1], vv[2], vv[3]));
@@ -1910,7 +1916,7 @@ DEV void dwb_rest(const DwBatch& bt, int rb, char* smem) {
   if (!r.ever) return;
   a.p = r.p + r.woff; a.g = r.g + r.woff; a.m = r.m + r.woff; a.v = r.v + r.woff;
   a.shadow = r.sh ? reinterpret_cast<bf16_t*>(r.sh) + r.woff : nullptr;
-  a.wd = 0.f; a.decoupled = 0;
+  a.wd = r.wwd; a.decoupled = bt.decoupled;  // (wwd != 0: decoupled only, the other rows decay lazily)
   a.touched = r.ever; a.now = r.now;
   const int lane = threadIdx.x & 63;
   const int nwaves = r.row_blocks * (NT / 64);
@@ -2660,6 +2666,7 @@ int fd_gemm_dw_batch(int n, const DwProb* probs, int K, const int* step, const f
     if (!hyper || !step || !rest->g || !rest->m || !rest->v || (rest->nruns > 0) != (rest->runs != nullptr) ||
         rest->n4 < 0 || (rest->ever && (rest->wrows <= 0 || rest->wrow4 <= 0 || rest->woff % 4)))
       return 7;
+    if ((rest->run_wd && !rest->runs) || (rest->ever && rest->wwd != 0.f && hyper[5] == 0.f)) return 8;
     bt.rest = *rest;
     // ~4 float4 per thread of the run table; one 64-row flag chunk per wave of the word table
     bt.rest.flat_blocks = rest->n4 > 0 ? (int)std::min<long long>(128, (rest->n4 + 2047) / 2048) : 0;

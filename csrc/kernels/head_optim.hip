@@ -180,12 +180,13 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a) {
     adam_flat4<NT, NTP>(a, vi, step_size, inv_sqrt_bc2);
 }
 
-// Adam over the rows of a table that have state (ever[row] != 0; weight decay 0): one wave per
+// Adam over the rows of a table that have state (ever[row] != 0): one wave per
 // row, which leaves at once unless the row is flagged, so every flagged row is updated in
 // parallel (row_len / 4 float4 per row, gradient 0 unless now[row]) with adam_kernel's
 // arithmetic (adam_math4: bitwise the dense launch's result).  The word-embedding table: ~30 k
 // rows, a few hundred of which a CICIDS2017 run ever touches; the dense launch walked all 23 M
-// parameters.
+// parameters.  Exact without weight decay; with decoupled decay the rows without state are owed
+// one multiplication per step, paid by adam_lazy_decay_kernel before anything reads them.
 __global__ __launch_bounds__(256) void adam_rows_kernel(AdamArgs a, int rows, int row4) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= rows || !a.touched[row]) return;  // wave-uniform
@@ -193,6 +194,53 @@ __global__ __launch_bounds__(256) void adam_rows_kernel(AdamArgs a, int rows, in
   adam_bias_corr(a.step, a.lr, a.b1, a.b2, step_size, inv_sqrt_bc2);
   if (row4 == 192) adam_row768(a, row, lane, step_size, inv_sqrt_bc2);
   else adam_row(a, 0, row, row4, lane, step_size, inv_sqrt_bc2);
+}
+
+// Lazy decoupled weight decay of table rows without Adam state (ever[row] == 0).  Such a row has
+// m = v = g = 0, so the dense AdamW step is exactly p *= 1 - lr * wd (adam_elem); done[row]
+// counts the steps whose multiplication the row has received.  One wave per entry of ids (the
+// rows a forward is about to gather; nullable = every row of the table): it raises done[row] to
+// the number of completed steps (step[0] - adj) with an atomic -- duplicate ids: one wave wins --
+// and applies the missing multiplications one by one (adam_decay: bitwise the dense launches),
+// writing the master and the bf16 shadow.
+struct LazyDecayArgs {
+  float* p;
+  bf16_t* shadow;  // nullable
+  int* done;
+  const unsigned char* ever;
+  const int* step;
+  int adj;
+  float lr, wd;
+  int rows, row4;
+  const void* ids;  // nullable
+  int ids64;
+  int n;            // entries of ids, or rows
+};
+
+__global__ __launch_bounds__(256) void adam_lazy_decay_kernel(LazyDecayArgs a) {
+  const int w = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (w >= a.n) return;  // wave-uniform, as every return below
+  long long row = w;
+  if (a.ids) row = a.ids64 ? static_cast<const long long*>(a.ids)[w] : (long long)static_cast<const int*>(a.ids)[w];
+  if (row < 0 || row >= a.rows || a.ever[row]) return;
+  const int target = a.step[0] - a.adj;
+  int old = 0;
+  if (lane == 0) old = atomicMax(a.done + row, target);
+  old = __shfl(old, 0);
+  const int k = target - old;
+  if (k <= 0) return;
+  for (int c = lane; c < a.row4; c += 64) {
+    const long long i = row * a.row4 + c;
+    float4 p = reinterpret_cast<const float4*>(a.p)[i];
+    for (int s = 0; s < k; ++s) {
+      adam_decay(a.lr, a.wd, p.x);
+      adam_decay(a.lr, a.wd, p.y);
+      adam_decay(a.lr, a.wd, p.z);
+      adam_decay(a.lr, a.wd, p.w);
+    }
+    reinterpret_cast<float4*>(a.p)[i] = p;
+    if (a.shadow) reinterpret_cast<uint2*>(a.shadow)[i] = make_uint2(pack_bf2(p.x, p.y), pack_bf2(p.z, p.w));
+  }
 }
 
 __global__ void step_kernel(int* step, uint32_t* seed) {
@@ -281,12 +329,15 @@ int fd_eval_metrics(const float* logits, const long long* labels, int B, double*
 int fd_adam(float* p, const float* g, float* m, float* v, void* shadow, long long n, const int* step, float lr,
             float b1, float b2, float eps, float wd, int decoupled, const unsigned char* touched,
             const unsigned char* now, long long skip_off, long long skip_rows, int row_len, const long long* runs,
-            int nruns, long long run_total4, hipStream_t st) {
+            int nruns, long long run_total4, const float* run_wd, hipStream_t st) {
   if (n % 4 != 0 || skip_off % 4 != 0 || row_len % 4 != 0) return 1;
-  if (wd != 0.f && touched) return 3;  // skipping untouched rows is exact only without weight decay
+  // skipping untouched rows is exact without weight decay; with decoupled decay the caller owes
+  // those rows their multiplications (fd_adam_lazy_decay)
+  if (wd != 0.f && touched && !decoupled) return 3;
+  if (run_wd && (touched || !runs)) return 5;
   if (runs && (nruns <= 0 || run_total4 <= 0)) return 4;
   AdamArgs a{p, g, m, v, (bf16_t*)shadow, runs ? run_total4 : n / 4, step, lr, b1, b2, eps, wd, decoupled,
-             skip_off / 4, (skip_off + skip_rows * row_len) / 4, row_len / 4, touched, now, runs, nruns};
+             skip_off / 4, (skip_off + skip_rows * row_len) / 4, row_len / 4, touched, now, runs, nruns, run_wd};
   const int grid = grid_for(n / 4);
   // FD_ADAM_NT: 0 = default cache policy, 1 = nontemporal g/m/v, 2 = also the fp32 master (default:
   // 2.336 vs 2.366-2.387 ms/step, profiles/r1_ab_adam_nt_master.txt -- only the bf16 shadow is re-read soon)
@@ -300,13 +351,29 @@ int fd_adam(float* p, const float* g, float* m, float* v, void* shadow, long lon
   return 0;
 }
 
-// Adam over the flagged rows of a [rows][row_len] table (weight decay 0; see adam_rows_kernel).
+// Adam over the flagged rows of a [rows][row_len] table (see adam_rows_kernel; wd != 0 only
+// decoupled: the unflagged rows' decay is applied lazily, fd_adam_lazy_decay).
 int fd_adam_rows(float* p, const float* g, float* m, float* v, void* shadow, int rows, int row_len, const int* step,
                  float lr, float b1, float b2, float eps, const unsigned char* ever, const unsigned char* now,
-                 hipStream_t st) {
+                 float wd, int decoupled, hipStream_t st) {
   if (row_len % 4 != 0 || rows <= 0 || !ever) return 1;
-  AdamArgs a{p, g, m, v, (bf16_t*)shadow, 0, step, lr, b1, b2, eps, 0.f, 0, 0, 0, row_len / 4, ever, now, nullptr, 0};
+  if (wd != 0.f && !decoupled) return 3;
+  AdamArgs a{p, g, m, v, (bf16_t*)shadow, 0, step, lr, b1, b2, eps, wd, decoupled, 0, 0, row_len / 4, ever, now,
+             nullptr, 0, nullptr};
   hipLaunchKernelGGL(adam_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, a, rows, row_len / 4);  // wave per row
+  return 0;
+}
+
+// The decoupled decay owed to the rows of a [rows][row_len] table without Adam state
+// (adam_lazy_decay_kernel): the rows named by the n entries of ids, or every row (ids == nullptr).
+int fd_adam_lazy_decay(float* p, void* shadow, int* done, const unsigned char* ever, int rows, int row_len,
+                       const int* step, int adj, float lr, float wd, const void* ids, int ids64, long long n,
+                       hipStream_t st) {
+  if (row_len % 4 != 0 || rows <= 0 || !p || !done || !ever || !step || adj < 0) return 1;
+  if (ids && (n <= 0 || n > (1ll << 30))) return 2;
+  LazyDecayArgs a{p, (bf16_t*)shadow, done, ever, step, adj, lr, wd, rows, row_len / 4, ids, ids64,
+                  ids ? (int)n : rows};
+  hipLaunchKernelGGL(adam_lazy_decay_kernel, dim3((a.n + 3) / 4), dim3(256), 0, st, a);
   return 0;
 }
 

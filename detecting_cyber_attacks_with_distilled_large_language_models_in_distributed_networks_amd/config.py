@@ -43,6 +43,7 @@ class FedConfig:
     eps: float = 1e-8
     weight_decay: float = 0.0
     decoupled_weight_decay: bool = False    # AdamW when True
+    no_decay: str = ""                      # comma-separated name substrings excluded from weight decay
     impl: str = "auto"                      # "hip" | "torch" | "auto" (hip on GPU)
     use_graph: bool = True                  # capture the train step in a HIP graph
     # --- federation (server.py:10-13) -------------------------------------------------

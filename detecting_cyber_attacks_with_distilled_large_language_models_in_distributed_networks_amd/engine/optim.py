@@ -41,10 +41,48 @@ the epilogues are staggered behind other tiles' MFMA work, and it does pay:
 2.034-2.039 (batched, unfused) vs 1.999-2.000 ms/step (batched + fused), against
 2.103 for the per-layer launches (profiles/r2_ab_dw_batch_fused_adam.txt).  On by
 default; ``fuse_dw=False`` for the unfused arm.
+
+Weight decay and parameter groups.  ``weight_decay`` follows ``torch.optim.Adam`` (coupled: the
+gradient gets ``wd * p``) or, with ``decoupled=True``, ``torch.optim.AdamW`` (``p *= 1 - lr * wd``
+before the update).  ``no_decay`` is a sequence of substrings matched against the arena's parameter
+names (the HF keys, e.g. ``...sa_layer_norm.weight``, ``...q_lin.bias``); matching parameters form a
+second group with decay 0 -- the usual recipe is ``no_decay=("bias", "LayerNorm", "layer_norm")``.
+Every launch that applies Adam honours the groups: the run-table launch and the rest blocks of the
+all-layer dW launch take a decay per run (runs are split at group boundaries), each fused dW
+epilogue takes its matrix's decay, and the qkv bias updated by the dW tiles takes the bias's.  (The
+q / k / v parameters of a block are one fused span: they must share a group.)  With
+``weight_decay == 0`` nothing changes, bit for bit.
+
+The sparse word-embedding table under weight decay:
+
+1. word table in the no-decay group: the row-flag path is exact as it is (coupled or decoupled);
+2. decoupled decay, word table decays: *lazy row decay*, exact to the bit.  A row never touched
+   since the moments were reset has m = v = g = 0, so its whole dense AdamW step is
+   ``p *= 1 - lr * wd``.  ``row_step`` (int32 per row, ~122 KB) counts the steps whose
+   multiplication a row without Adam state has received.  Before the embedding gather of every
+   training forward (HIP path) a small launch (``lazy_catchup``; csrc/kernels/head_optim.hip
+   adam_lazy_decay_kernel) pays the batch's rows what they are owed -- the number of completed
+   steps comes from the device step counter, so it replays inside a captured graph -- and from
+   its first gradient a row is updated every step by the row-flag Adam with the real decay.
+   The invariant: a row without state that nothing has read since step ``row_step[row]`` is
+   ``step - row_step[row]`` multiplications behind.  ``finish()`` settles every row (one launch;
+   idempotent; free when no step ran since the last one -- a host-side check) and runs at every
+   flush point: ``train_model`` before each ``on_epoch`` callback and before it returns,
+   ``state_dict()`` / ``load_state_dict()`` / ``reset_state()`` here, and the model's
+   ``state_dict()`` (a hook this optimizer registers).  The other readers of ``arena.master`` --
+   FedAvg (parallel/fedavg.py) and the federated runner's exchanges, model sharing and virtual
+   clients (fed/runner.py) -- all run after ``train_model`` has returned, i.e. after a flush; code
+   that reads ``arena.master`` between the steps of its own loop calls ``finish()`` first;
+3. coupled (L2) decay, word table decays: the gradient ``wd * p`` is non-zero for every row, so
+   nothing can be skipped -- the dense word gradient and the dense table update, as before.
+
+Data-parallel replicas (parallel/dp.py) exchange row flags, which the lazy decay does not cover:
+``make_dp_step_fn`` switches a decaying word table to the dense path (``dense_word_decay()``).
 """
 from __future__ import annotations
 
 import math
+import weakref
 from typing import Optional
 
 import torch
@@ -53,24 +91,150 @@ import torch
 class ArenaAdam:
     def __init__(self, model, lr: float = 2e-5, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, decoupled: bool = False, overlap: bool = False,
-                 fuse_dw: bool = True):
+                 fuse_dw: bool = True, no_decay=()):
+        if not (math.isfinite(weight_decay) and weight_decay >= 0.0):
+            raise ValueError(f"weight_decay must be finite and >= 0, got {weight_decay}")
+        if isinstance(no_decay, str):
+            no_decay = no_decay.split(",")
         self.model = model
         self.overlap = overlap
         self.fuse_dw = fuse_dw
         self._run_tables = {}
+        self._run_decays = {}
         self.arena = model.arena
         self.lr, self.betas, self.eps = lr, tuple(betas), eps
         self.weight_decay, self.decoupled = weight_decay, decoupled
-        if weight_decay != 0.0 and getattr(model, "sparse_word_grad", False):
-            model.sparse_word_grad = False  # AdamW decays every row: keep the dense word gradient
-            model._hip_cache = None
+        self.no_decay = tuple(s.strip() for s in no_decay if s and s.strip())
+        self._build_groups()
+        prev = getattr(model, "_lazy_decay_opt", None)
+        prev = prev() if prev is not None else None
+        if prev is not None and prev is not self:
+            prev.finish()  # (an earlier optimizer of this model may still owe its rows their decay)
+        self._dense_word = False
+        if self.word_wd != 0.0 and not decoupled:
+            self.dense_word_decay()  # L2 decay reaches every row: keep the dense word gradient
         self._alloc()
+        if hasattr(model, "word_embedding_span"):
+            model._lazy_decay_opt = weakref.ref(self)
+            if not getattr(model, "_lazy_decay_hook", False) and hasattr(model, "register_state_dict_pre_hook"):
+                model.register_state_dict_pre_hook(_flush_before_state_dict)
+                model._lazy_decay_hook = True
+
+    # -------------------------------------------------------------- parameter groups
+    def _build_groups(self):
+        """Decay segments [(start, end, wd)] covering the arena, ascending and merged (a
+        parameter's alignment padding -- zeros with zero gradient -- joins its parameter)."""
+        A = self.arena
+        segs = []
+        for name, (off, _shape) in sorted(A.offsets.items(), key=lambda kv: kv[1][0]):
+            wd = 0.0 if any(s in name for s in self.no_decay) else float(self.weight_decay)
+            if segs and segs[-1][2] == wd:
+                continue
+            if segs:
+                segs[-1][1] = off
+            segs.append([off, A.numel, wd])
+        if not segs:
+            segs = [[0, A.numel, float(self.weight_decay)]]
+        segs[0][0] = 0
+        segs[-1][1] = A.numel
+        self._segs = [tuple(s) for s in segs]
+        # groups in effect: the launches take per-run / per-problem decays instead of the scalar
+        self.grouped_decay = any(wd != float(self.weight_decay) for _, _, wd in self._segs)
+        self.word_wd = 0.0
+        if hasattr(self.model, "word_embedding_span"):
+            woff, rows, rl = self.model.word_embedding_span()
+            self.word_wd = self._span_decay(woff, rows * rl)
+
+    def _span_decay(self, off: int, n: int) -> float:
+        """The weight decay of elements [off, off + n): they must lie in one group."""
+        wds = {wd for a, b, wd in self._segs if a < off + n and off < b}
+        if len(wds) != 1:
+            raise ValueError("a span updated by one launch mixes weight-decay groups (q / k / v of a block "
+                             "must share a group)")
+        return wds.pop()
+
+    def decays_of(self, grads):
+        """The weight decay of each arena gradient view's parameters."""
+        A = self.arena
+        base = A.grad.data_ptr()
+        return [self._span_decay((g.data_ptr() - base) // A.grad.element_size(), g.numel()) for g in grads]
+
+    def _split_groups(self, runs):
+        """Runs split at group boundaries, and each piece's decay."""
+        out, wds = [], []
+        for off, n in runs:
+            for a, b, wd in self._segs:
+                lo, hi = max(off, a), min(off + n, b)
+                if lo < hi:
+                    out.append((lo, hi - lo))
+                    wds.append(wd)
+        return out, wds
+
+    # -------------------------------------------------------------- sparse word table under decay
+    def dense_word_decay(self):
+        """Give up the sparse word-embedding path when the word table decays (coupled decay, or a
+        step function whose row flags the lazy decay does not cover: data-parallel replicas)."""
+        if self.word_wd == 0.0:
+            return
+        self.finish()
+        self._dense_word = True
+        if getattr(self.model, "sparse_word_grad", False):
+            self.model.sparse_word_grad = False
+            self.model._hip_cache = None
+
+    def lazy_active(self) -> bool:
+        """Whether rows of the word table without Adam state decay lazily (case 2 above)."""
+        m = self.model
+        return (self.word_wd != 0.0 and self.decoupled and not self._dense_word
+                and getattr(self, "row_step", None) is not None
+                and getattr(m, "impl", None) == "hip" and getattr(m, "sparse_word_grad", False)
+                and getattr(m, "emb_ever", None) is not None)
+
+    def _word_views(self):
+        A = self.arena
+        woff, rows, rl = self.model.word_embedding_span()
+        sl = slice(woff, woff + rows * rl)
+        return A.master[sl], (A.shadow[sl] if A.shadow is not None else None), rl
+
+    def lazy_catchup(self, ids):
+        """Before a training forward gathers rows ``ids``: pay those without Adam state the decay
+        of the steps completed so far (the model's HIP forward calls this; replays inside a graph)."""
+        if not self.lazy_active():
+            return
+        from ..ops import kernels as K
+        p, sh, rl = self._word_views()
+        # (inside a step the counter already counts the running one)
+        K.adam_lazy_decay(p, sh, self.row_step, self.model.emb_ever, self.step_t, 1 if self._begun else 0,
+                          self.lr, self.word_wd, rl, ids if ids.is_contiguous() else ids.contiguous())
+
+    def finish(self):
+        """Settle the lazy decay: every word row without Adam state is brought up to the current
+        step (one launch).  Idempotent; returns at once when no step ran since the last flush."""
+        if not getattr(self, "_lazy_pending", False):
+            return
+        if not self.lazy_active():
+            self._lazy_pending = False
+            return
+        from ..ops import kernels as K
+        p, sh, rl = self._word_views()
+        K.adam_lazy_decay(p, sh, self.row_step, self.model.emb_ever, self.step_t, 1 if self._begun else 0,
+                          self.lr, self.word_wd, rl, None)
+        self.model.mark_shadow_synced()
+        self._lazy_pending = self._begun
+
+    def note_step(self):
+        """A step is about to run outside this object's sight (a graph replay): decay is pending."""
+        self._lazy_pending = True
 
     def _alloc(self):
         dev = self.arena.device
         self.m = torch.zeros_like(self.arena.master)
         self.v = torch.zeros_like(self.arena.master)
         self.step_t = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.row_step = None  # lazy decay: steps whose decay each word row without state has received
+        if dev.type == "cuda" and hasattr(self.model, "word_embedding_span"):
+            self.row_step = torch.zeros(self.model.word_embedding_span()[1], dtype=torch.int32, device=dev)
+        self._lazy_pending = False
         self.host_step = 0
         self._begun = False
         self._done = []  # (offset, length) spans already updated this step
@@ -90,6 +254,7 @@ class ArenaAdam:
         the (step, seed) counters to advance there instead of launching -- the caller folds them
         into a launch it makes anyway before anything reads them (the packing kernel)."""
         from ..ops import kernels as K
+        self._lazy_pending = True
         if not self._begun:
             if defer is not None:
                 defer.append((self.step_t, seed))
@@ -108,14 +273,15 @@ class ArenaAdam:
         A = self.arena
         b1, b2 = self.betas
         sl = slice(off, off + n)
+        wd = self._span_decay(off, n) if self.grouped_decay else self.weight_decay
         if sparse:
             woff, rows, rl = self.model.word_embedding_span()
             K.adam(A.master[sl], A.grad[sl], self.m[sl], self.v[sl], A.shadow[sl], self.step_t, self.lr, b1, b2,
-                   self.eps, self.weight_decay, self.decoupled, self.model.emb_ever, self.model.emb_now, woff - off,
+                   self.eps, wd, self.decoupled, self.model.emb_ever, self.model.emb_now, woff - off,
                    rows, rl)
         else:
             K.adam(A.master[sl], A.grad[sl], self.m[sl], self.v[sl], A.shadow[sl], self.step_t, self.lr, b1, b2,
-                   self.eps, self.weight_decay, self.decoupled)
+                   self.eps, wd, self.decoupled)
 
     def _on_layer_grads(self, i: int):
         """Backward hook: block i's gradients are final -> update it on the side stream."""
@@ -129,7 +295,8 @@ class ArenaAdam:
         cur = torch.cuda.current_stream(self.arena.device)
         self._side.wait_stream(cur)
         with torch.cuda.stream(self._side):
-            self._update(off, n, False)
+            for o, k in (self._split_groups([(off, n)])[0] if self.grouped_decay else [(off, n)]):
+                self._update(o, k, False)
         self._done.append((off, n))
 
     def can_fuse(self) -> bool:
@@ -172,10 +339,30 @@ class ArenaAdam:
             from ..ops import kernels as K
             t = K.adam_runs(runs, self.arena.device)
             self._run_tables[key] = t
+            if self.grouped_decay:
+                self._run_decays[key] = K.adam_run_decay([self._span_decay(o, n) for o, n in runs],
+                                                         self.arena.device)
         return t
+
+    def _runs_decay(self, runs):
+        """The per-run decays that go with ``_runs_table(runs)`` (None: one group)."""
+        return self._run_decays.get(tuple(runs))
+
+    def rest_decay_args(self):
+        """Keyword arguments of ``gemm_dw_batch`` for the decays of the rest ``rest_args`` returned."""
+        kw = {}
+        rd = self._runs_decay(self._rest_key) if self.grouped_decay else None
+        if rd is not None:
+            kw["rest_wd"], kw["rest_wd_host"] = rd
+        if self.word_wd != 0.0:
+            kw["word_wd"] = self.word_wd
+        return kw
 
     def reset_state(self):
         """FedAvg rounds restart the moments (the reference re-creates Adam each run)."""
+        self.finish()
+        if self.row_step is not None:
+            self.row_step.zero_()
         self.m.zero_()
         self.v.zero_()
         self.step_t.zero_()
@@ -207,11 +394,13 @@ class ArenaAdam:
         # "HIP learns faster than fp32" loss-curve bias was exactly that: the fp32 reference
         # arm on the GPU never updated its word embeddings -- results/numerics_r4/.)
         hip_sparse = getattr(self.model, "impl", None) == "hip" and getattr(self.model, "sparse_word_grad", False)
-        sparse = (hip_sparse and self.weight_decay == 0.0
+        # exact when the word table does not decay; with decoupled decay the rows without state
+        # decay lazily (lazy_catchup / finish); coupled decay needs the dense table
+        sparse = (hip_sparse and (self.word_wd == 0.0 or self.lazy_active())
                   and getattr(self.model, "emb_ever", None) is not None)
         if hip_sparse and not sparse and getattr(self.model, "emb_now", None) is not None:
-            raise RuntimeError("sparse word-embedding grads need weight_decay == 0 "
-                               "(set model.sparse_word_grad = False for AdamW)")
+            raise RuntimeError("sparse word-embedding grads with a decaying word table need decoupled "
+                               "weight decay (set model.sparse_word_grad = False otherwise)")
         return sparse
 
     def _rest_runs(self, sparse: bool):
@@ -226,6 +415,8 @@ class ArenaAdam:
             pos = max(pos, off + n)
         if pos < A.numel:
             runs.append((pos, A.numel - pos))
+        if self.grouped_decay:
+            runs, _ = self._split_groups(runs)
         if not sparse:
             return runs, None
         woff, rows, rl = self.model.word_embedding_span()
@@ -266,6 +457,7 @@ class ArenaAdam:
             return None
         woff, rows, rl = self.model.word_embedding_span()
         tab, total4, _ = table
+        self._rest_key = tuple(rest)
         self._rest_in_launch = True
         return ([A.master, A.grad, self.m, self.v, A.shadow, tab, self.model.emb_ever, self.model.emb_now],
                 [total4, woff, rows, rl])
@@ -300,11 +492,11 @@ class ArenaAdam:
                 wend = woff + rows * rl
                 sl = slice(woff, wend)
                 K.adam_rows(A.master[sl], A.grad[sl], self.m[sl], self.v[sl], A.shadow[sl], self.step_t, self.lr, b1,
-                            b2, self.eps, self.model.emb_ever, self.model.emb_now, rl)
+                            b2, self.eps, self.model.emb_ever, self.model.emb_now, rl, self.word_wd, self.decoupled)
                 rest_table = self._runs_table(rest) if len(rest) > 1 else None
                 if rest_table is not None:
                     K.adam(A.master, A.grad, self.m, self.v, A.shadow, self.step_t, self.lr, b1, b2, self.eps,
-                           self.weight_decay, self.decoupled, runs=rest_table)
+                           self.weight_decay, self.decoupled, runs=rest_table, run_decay=self._runs_decay(rest))
                 else:
                     for off, n in rest:
                         self._update(off, n, False)
@@ -312,7 +504,7 @@ class ArenaAdam:
                 from ..ops import kernels as K
                 b1, b2 = self.betas
                 K.adam(A.master, A.grad, self.m, self.v, A.shadow, self.step_t, self.lr, b1, b2, self.eps,
-                       self.weight_decay, self.decoupled, runs=table)
+                       self.weight_decay, self.decoupled, runs=table, run_decay=self._runs_decay(runs))
             else:
                 for off, n in runs:
                     self._update(off, n, sparse and off <= woff < off + n)
@@ -326,7 +518,17 @@ class ArenaAdam:
         t = self.host_step
         self.step_t += 1
         p, g = A.master, A.grad
-        if self.weight_decay:
+        if self.weight_decay and self.grouped_decay:  # one group per segment, as torch.optim's param groups
+            if not self.decoupled:
+                g = g.clone()
+            for a, b, wd in self._segs:
+                if wd == 0.0:
+                    continue
+                if self.decoupled:
+                    p[a:b].mul_(1 - self.lr * wd)
+                else:
+                    g[a:b] += wd * p[a:b]
+        elif self.weight_decay:
             if self.decoupled:
                 p.mul_(1 - self.lr * self.weight_decay)
             else:
@@ -340,14 +542,24 @@ class ArenaAdam:
         self.model.mark_shadow_synced()
 
     def state_dict(self):
+        self.finish()
         return {"m": self.m.cpu(), "v": self.v.cpu(), "step": int(self.step_t.item()),
                 "lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.weight_decay,
                 "decoupled": self.decoupled}
 
     def load_state_dict(self, sd):
+        self.finish()  # (before every row counts as having state)
         if getattr(self.model, "emb_ever", None) is not None:
             self.model.emb_ever.fill_(1)  # unknown history: treat every row as having state
         self.m.copy_(sd["m"])
         self.v.copy_(sd["v"])
         self.step_t.fill_(int(sd["step"]))
         self.host_step = int(sd["step"])
+
+
+def _flush_before_state_dict(module, *_args, **_kw):
+    """``state_dict`` pre-hook of a model whose optimizer decays word rows lazily."""
+    ref = getattr(module, "_lazy_decay_opt", None)
+    opt = ref() if ref is not None else None
+    if opt is not None:
+        opt.finish()

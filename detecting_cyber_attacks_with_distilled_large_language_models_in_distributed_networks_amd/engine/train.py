@@ -55,6 +55,16 @@ def _one(device) -> torch.Tensor:
     return unit_grad(device)
 
 
+def _prepare(models, optimizer):
+    """What a graph replay of a step needs done eagerly first: the models' ``prepare_replay`` and
+    the optimizer's note that a step runs (its lazy weight decay is then pending: ``finish()``)."""
+    preps = [f for f in (getattr(m, "prepare_replay", None) for m in models) if f]
+    note = getattr(optimizer, "note_step", None)
+    if note is not None:
+        preps.append(note)
+    return (lambda: [f() for f in preps]) if preps else None
+
+
 def make_step_fn(model, optimizer, criterion=None):
     fused = criterion is None or isinstance(criterion, torch.nn.CrossEntropyLoss)
 
@@ -69,7 +79,7 @@ def make_step_fn(model, optimizer, criterion=None):
         optimizer.step()
         return loss.detach()
 
-    step.prepare = getattr(model, "prepare_replay", None)
+    step.prepare = _prepare([model], optimizer)
     return step
 
 
@@ -89,9 +99,16 @@ def make_kd_step_fn(student, teacher, optimizer, temperature: float = 2.0, alpha
         optimizer.step()
         return loss.detach()
 
-    preps = [f for f in (getattr(student, "prepare_replay", None), getattr(teacher, "prepare_replay", None)) if f]
-    step.prepare = (lambda: [f() for f in preps]) if preps else None
+    step.prepare = _prepare([student, teacher], optimizer)
     return step
+
+
+def _finish(optimizer):
+    """Settle an optimizer's deferred work (ArenaAdam's lazy word-row decay) before anything
+    outside the step reads the weights; free when nothing is pending."""
+    fin = getattr(optimizer, "finish", None)
+    if fin is not None:
+        fin()
 
 
 def _check_native(model):
@@ -160,10 +177,12 @@ def train_model(model, train_loader, criterion=None, optimizer=None, num_epochs:
         if log:
             log.info(f"Epoch [{epoch + 1}/{num_epochs}], Average Loss: {avg:.4f}",
                      batches=nb, seconds=dt, batches_per_sec=nb / dt if dt > 0 else 0.0)
+        _finish(optimizer)  # (the callback may evaluate or checkpoint the model)
         if on_epoch:
             on_epoch(epoch, avg)
         if max_steps is not None and steps >= max_steps:
             break
+    _finish(optimizer)
     if dev.type == "cuda":
         torch.cuda.synchronize()
     total = time.perf_counter() - t0

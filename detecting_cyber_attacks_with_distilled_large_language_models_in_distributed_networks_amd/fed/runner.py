@@ -37,6 +37,14 @@ from ..utils.metrics import save_metrics
 from ..utils.timers import PhaseTimer
 
 
+def make_optimizer(model, cfg: FedConfig) -> ArenaAdam:
+    """The client optimizer of a run: Adam / AdamW with the configuration's hyper-parameters and
+    its no-decay parameter group (``--no-decay bias,LayerNorm,layer_norm``)."""
+    return ArenaAdam(model, lr=cfg.lr, betas=cfg.betas, eps=cfg.eps, weight_decay=cfg.weight_decay,
+                     decoupled=cfg.decoupled_weight_decay,
+                     no_decay=tuple(x.strip() for x in cfg.no_decay.split(",") if x.strip()))
+
+
 def _metrics_record(m) -> Dict:
     return {"accuracy": float(m[0]), "loss": float(m[1]), "precision": float(m[2]), "recall": float(m[3]),
             "f1": float(m[4]), "confusion_matrix": [[int(x) for x in row] for row in m[5]]}
@@ -186,8 +194,7 @@ class FederatedClient:
     def run_round(self, r: int) -> Dict:
         cfg, log, model = self.cfg, self.log, self.model
         log.phase(f"Starting round {r + 1}/{cfg.rounds}")
-        opt = ArenaAdam(model, lr=cfg.lr, betas=cfg.betas, eps=cfg.eps, weight_decay=cfg.weight_decay,
-                        decoupled=cfg.decoupled_weight_decay)
+        opt = make_optimizer(model, cfg)
         opt.reset_state()  # a fresh Adam every round (client1.py:380), "has state" row flags included
         opt_path = os.path.join(cfg.out_dir, f"client{self.client_id}_optim.pth")
         if cfg.save_optimizer and r == self.start_round:
@@ -374,8 +381,7 @@ def warm_start(client: "FederatedClient", epochs: int = 1, rows: int = 225_745, 
     data = build_client_data(frame, 0, fraction, cfg.base_seed + 1000, cfg.max_len, client.tokenizer)
     dev = model.device
     loader = DeviceLoader(data.train, cfg.batch_size, shuffle=True, device=dev, seed=cfg.base_seed + 1000)
-    opt = ArenaAdam(model, lr=cfg.lr, betas=cfg.betas, eps=cfg.eps, weight_decay=cfg.weight_decay,
-                    decoupled=cfg.decoupled_weight_decay)
+    opt = make_optimizer(model, cfg)
     opt.reset_state()
     tr = train_model(model, loader, None, opt, epochs, log=client.log, use_graph=cfg.use_graph)
     test = _metrics_record(evaluate_model(model, DeviceLoader(data.test, cfg.eval_batch_size, device=dev),
@@ -474,8 +480,7 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
                 model.rng.copy_(c["rng"])
             model.torch_counter = c["torch_counter"]
             model.sync_shadow(force=True)
-            opt = ArenaAdam(model, lr=cfg.lr, betas=cfg.betas, eps=cfg.eps, weight_decay=cfg.weight_decay,
-                            decoupled=cfg.decoupled_weight_decay)
+            opt = make_optimizer(model, cfg)
             opt.reset_state()  # (also clears the sparse word rows' "has Adam state" flags)
             tr = train_model(model, loader, None, opt, cfg.epochs, log=client.log, use_graph=cfg.use_graph,
                              teacher=teacher, kd_temperature=cfg.kd_temperature, kd_alpha=cfg.kd_alpha)

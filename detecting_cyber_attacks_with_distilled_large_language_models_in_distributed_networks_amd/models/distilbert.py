@@ -533,6 +533,15 @@ class DDoSClassifier(nn.Module):
             # before the step; the all-layer dW launch runs after every dX GEMM of the backward)
             rc.fused_adam = self.fused_opt
         plan = self._prune_plan(rc, layers, grad)
+        # an AdamW optimizer that decays the untouched word rows lazily (engine/optim.py): the rows
+        # a training forward gathers are paid what they are owed first (before the step counter
+        # advances).  Other forwards read flushed weights (ArenaAdam.finish); their captured graphs
+        # (engine/infer.py) may outlive the optimizer, so they must not hold its buffers.
+        if grad and self.training:
+            lazy = getattr(self, "_lazy_decay_opt", None)
+            lazy = lazy() if lazy is not None else None
+            if lazy is not None:
+                lazy.lazy_catchup(ids)
         # packed step: the counters ride on the packing launch (no kernel of their own)
         incs = [] if packed and self.fold_step_counters else None
         if self.training:

@@ -215,6 +215,9 @@ def linear_dw_batch(jobs: list, adam=None, cfg: int = -1, opt=None):
         st, hp = adam(outs) if adam is not None else ([], [])
         bias = [j[4] if len(j) > 4 else None for j in chunk]
         rest = None
+        # parameter groups (ArenaAdam(no_decay=)): each matrix's and each in-launch bias's decay
+        groups = opt is not None and adam is not None and getattr(opt, "grouped_decay", False)
+        extra = {"decay": opt.decays_of(outs)} if groups else {}
         if adam is not None and opt is not None and ADAM_IN_DW and i == starts[-1]:
             # the qkv biases summed by this launch are updated by its tiles when it also finishes
             # the step: mark them, then hand the rest of the step to the launch
@@ -224,13 +227,17 @@ def linear_dw_batch(jobs: list, adam=None, cfg: int = -1, opt=None):
             rest = opt.rest_args()
             if rest is None:
                 del opt._done[done0:]  # (step() updates them after all)
+            else:
+                if groups:
+                    extra["bias_decay"] = [opt.decays_of([b])[0] if b is not None else 0.0 for b in bias]
+                extra.update(opt.rest_decay_args())
         if any(b is not None for b in bias):
             none = torch.empty(0, dtype=torch.float32, device=outs[0].device)
             bias = [b if b is not None else none for b in bias]
         else:
             bias = []
         ext().gemm_dw_batch([j[0] for j in chunk], [j[1] for j in chunk], outs, [int(j[3]) for j in chunk],
-                            st, hp, cfg, bias, *(rest if rest is not None else ([], [])))
+                            st, hp, cfg, bias, *(rest if rest is not None else ([], [])), **extra)
 
 
 # The qkv bias gradient from the all-layer dW launch itself: the qkv weight gradient's tiles of the
@@ -988,20 +995,37 @@ def eval_metrics(logits, labels, acc, counts, prob1=None, preds=None):
 
 
 def adam(p, g, m, v, shadow, step, lr, b1, b2, eps, wd, decoupled, touched=None, now=None, skip_off=0, skip_rows=0,
-         row_len=4, runs=None):
+         row_len=4, runs=None, run_decay=None):
     """Flat-arena Adam.  touched/now (uint8 row flags over [skip_off, skip_off+skip_rows*row_len)) let
-    the kernel skip rows with zero state and zero gradient (exact for weight_decay == 0).
+    the kernel skip rows with zero state and zero gradient (exact for weight_decay == 0; with
+    decoupled decay the caller owes those rows ``adam_lazy_decay``).
     runs = (device int64 [n, 3] table, total float4s, largest end float4) from ``adam_runs``:
-    update only those element runs, in one launch."""
+    update only those element runs, in one launch.  run_decay = (device fp32 [n], the same values
+    as a list) from ``adam_run_decay``: a weight decay per run (parameter groups) instead of wd."""
     table, total4, end4 = runs if runs is not None else (None, 0, 0)
+    rwd, rwd_host = run_decay if run_decay is not None else (None, [])
     ext().adam(p, g, m, v, shadow, step, lr, b1, b2, eps, wd, decoupled, touched, now, skip_off, skip_rows, row_len,
-               table, total4, end4)
+               table, total4, end4, rwd, rwd_host)
 
 
-def adam_rows(p, g, m, v, shadow, step, lr, b1, b2, eps, ever, now, row_len):
-    """Adam (weight decay 0) over the rows of one [rows][row_len] table (views of the arenas)
-    whose ``ever`` flag is set -- the sparse word-embedding update, one wave per 64 row flags."""
-    ext().adam_rows(p, g, m, v, shadow, step, lr, b1, b2, eps, ever, now, row_len)
+def adam_rows(p, g, m, v, shadow, step, lr, b1, b2, eps, ever, now, row_len, wd=0.0, decoupled=False):
+    """Adam over the rows of one [rows][row_len] table (views of the arenas) whose ``ever`` flag
+    is set -- the sparse word-embedding update, one wave per 64 row flags.  wd != 0 needs
+    decoupled decay; the rows without state then decay through ``adam_lazy_decay``."""
+    ext().adam_rows(p, g, m, v, shadow, step, lr, b1, b2, eps, ever, now, row_len, wd, decoupled)
+
+
+def adam_lazy_decay(p, shadow, done, ever, step, adj, lr, wd, row_len, ids=None):
+    """The decoupled decay owed to rows of one [rows][row_len] table that have no Adam state:
+    rows ``ids`` (none: every row) are multiplied by 1 - lr * wd once per step not yet applied,
+    up to step - adj completed steps; ``done`` (int32 per row) keeps the count."""
+    ext().adam_lazy_decay(p, shadow, done, ever, step, adj, lr, wd, row_len, ids)
+
+
+def adam_run_decay(decays, device):
+    """Per-run weight decays for ``adam(run_decay=)``: (device fp32 tensor, the values)."""
+    vals = [float(d) for d in decays]
+    return torch.tensor(vals, dtype=torch.float32, device=device), vals
 
 
 def adam_runs(spans, device):

@@ -256,6 +256,11 @@ def make_dp_step_fn(model, optimizer, sync: GradSync, teacher=None, temperature:
     the shard shares, sum to the client-batch KD loss exactly as the CE loss does."""
     if getattr(optimizer, "overlap", False):
         raise ValueError("data-parallel clients need ArenaAdam(overlap=False)")
+    # a decaying word table: the replicas' exchanged row flags are outside the lazy row decay
+    # (engine/optim.py), so the dense table is decayed and updated instead
+    dense = getattr(optimizer, "dense_word_decay", None)
+    if dense is not None:
+        dense()
     def step(ids, mask, labels, tokens=None):  # shards run the padded path (no per-shard token count)
         optimizer.zero_grad()
         if teacher is None:
