@@ -43,7 +43,7 @@ int fd_gemm_dw2(const void* A0, const void* B0, float* C0, int M0, int N0, const
                 const FdAdamEpi* adams, int defer, int* splits_out, hipStream_t st);
 int fd_gemm_dw2_splits(int M0, int N0, int M1, int N1, int K);
 int fd_gemm_dw_batch(int n, const FdDwProb* probs, int K, const int* step, const float* hyper, int cfg,
-                     const FdAdamRest* rest, hipStream_t st);
+                     const FdAdamRest* rest, const FdLrSched* sched, hipStream_t st);
 int fd_gemm_ln_set_diag(int diag);
 int fd_gemm_dwb_set_mix(int mode);
 long long fd_gemm_dwb_mixed_launches();
@@ -135,13 +135,14 @@ int fd_eval_metrics(const float* logits, const long long* labels, int B, double*
 int fd_adam(float* p, const float* g, float* m, float* v, void* shadow, long long n, const int* step, float lr,
             float b1, float b2, float eps, float wd, int decoupled, const unsigned char* touched,
             const unsigned char* now, long long skip_off, long long skip_rows, int row_len, const long long* runs,
-            int nruns, long long run_total4, const float* run_wd, hipStream_t st);
+            int nruns, long long run_total4, const float* run_wd, const FdLrSched* sched, hipStream_t st);
 int fd_adam_rows(float* p, const float* g, float* m, float* v, void* shadow, int rows, int row_len, const int* step,
                  float lr, float b1, float b2, float eps, const unsigned char* ever, const unsigned char* now,
-                 float wd, int decoupled, hipStream_t st);
+                 float wd, int decoupled, const FdLrSched* sched, hipStream_t st);
 int fd_adam_lazy_decay(float* p, void* shadow, int* done, const unsigned char* ever, int rows, int row_len,
                        const int* step, int adj, float lr, float wd, const void* ids, int ids64, long long n,
-                       hipStream_t st);
+                       const FdLrSched* sched, hipStream_t st);
+int fd_lr_schedule_table(float* out, int n, float lr, const FdLrSched* sched, hipStream_t st);
 int fd_step(int* step, uint32_t* seed, hipStream_t st);
 int fd_scale_cast(float* p, void* shadow, long long n, float scale, hipStream_t st);
 int fd_axpby(float* dst, const float* x, const float* y, float a, float b, long long n, hipStream_t st);
@@ -358,6 +359,25 @@ void need_decays(const std::vector<double>& wd, size_t n, const char* what) {
   for (double w : wd) TORCH_CHECK(std::isfinite(w) && w >= 0.0, what, ": a weight decay must be finite and >= 0");
 }
 
+// A learning-rate schedule argument: empty (constant) or [kind, warmup, total, offset] (FdLrSched,
+// adam_epi.h; the launch's lr is its base rate).
+FdLrSched need_sched(const std::vector<int64_t>& sched, double lr, const char* what) {
+  TORCH_CHECK(std::isfinite(lr), what, ": lr must be finite");
+  FdLrSched s{};
+  if (sched.empty()) return s;
+  TORCH_CHECK(sched.size() == 4, what, ": sched is [kind, warmup, total, offset], got ", sched.size(), " entries");
+  const int64_t lim = int64_t(1) << 30;  // (offset + step and total - warmup stay inside int32)
+  TORCH_CHECK(sched[0] >= 0 && sched[0] <= 2, what, ": sched kind must be 0 (constant), 1 (linear) or 2 "
+              "(constant with warmup), got ", sched[0]);
+  TORCH_CHECK(sched[1] >= 0 && sched[1] < lim, what, ": sched warmup must be >= 0 and < 2^30, got ", sched[1]);
+  TORCH_CHECK(sched[2] >= 0 && sched[2] < lim, what, ": sched total must be >= 0 and < 2^30, got ", sched[2]);
+  TORCH_CHECK(sched[3] >= 0 && sched[3] < lim, what, ": sched offset must be >= 0 and < 2^30, got ", sched[3]);
+  TORCH_CHECK(sched[0] != 1 || sched[1] <= sched[2], what, ": sched warmup (", sched[1], ") must be <= total (",
+              sched[2], ") for the linear schedule");
+  s.kind = (int)sched[0]; s.warmup = (int)sched[1]; s.total = (int)sched[2]; s.offset = (int)sched[3];
+  return s;
+}
+
 // Every weight gradient of a backward in one launch (gemm.hip gemm_dw_batch_kernel):
 // Cs[i] (+)= As[i]^T Bs[i] (fp32), As[i] [K_i][M_i], Bs[i] [K_i][N_i] bf16 (K_i % 64 == 0).
 // adam: empty, or [p, m, v, shadow] per problem + the device step counter last (fused
@@ -369,7 +389,9 @@ void gemm_dw_batch(const std::vector<at::Tensor>& As, const std::vector<at::Tens
                    const std::vector<int64_t>& rest_i = {}, const std::vector<double>& decay = {},
                    const std::vector<double>& bias_decay = {},
                    const c10::optional<at::Tensor>& rest_wd = c10::nullopt,
-                   const std::vector<double>& rest_wd_host = {}, double word_wd = 0.0) {
+                   const std::vector<double>& rest_wd_host = {}, double word_wd = 0.0,
+                   const std::vector<int64_t>& sched = {}) {
+  // sched (with adam): the learning-rate schedule whose base rate hp[0] is (need_sched)
   // decay / bias_decay (with adam): per problem the weight decay of its matrix / of its bias
   // (parameter groups; empty = hp's for all).  rest_wd: per-run weight decay of the rest's run
   // table (device fp32 [nruns]) with the same values in rest_wd_host (checked here); word_wd: the
@@ -413,6 +435,8 @@ void gemm_dw_batch(const std::vector<at::Tensor>& As, const std::vector<at::Tens
     TORCH_CHECK(biases[i].numel() == As[i].size(1), "gemm_dw_batch: a bias has the M entries of its problem");
     pr[i].bias = biases[i].data_ptr<float>();
   }
+  TORCH_CHECK(!adam.empty() || sched.empty(), "gemm_dw_batch: sched needs the fused Adam");
+  const FdLrSched sc = need_sched(sched, adam.empty() || hp.empty() ? 0.0 : hp[0], "gemm_dw_batch");
   std::vector<FdAdamEpi> ad(n);
   const int* step = nullptr;
   float hyper[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -482,7 +506,7 @@ void gemm_dw_batch(const std::vector<at::Tensor>& As, const std::vector<at::Tens
       }
   }
   check_rc(fd_gemm_dw_batch((int)n, pr.data(), (int)K, step, adam.empty() ? nullptr : hyper, (int)cfg,
-                            rest.empty() ? nullptr : &rs, stream()),
+                            rest.empty() ? nullptr : &rs, &sc, stream()),
            "gemm_dw_batch");
 }
 
@@ -1553,7 +1577,9 @@ void adam(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, const a
           double wd, bool decoupled, const c10::optional<at::Tensor>& touched, const c10::optional<at::Tensor>& now,
           int64_t skip_off, int64_t skip_rows, int64_t row_len, const c10::optional<at::Tensor>& runs,
           int64_t run_total4, int64_t run_end4, const c10::optional<at::Tensor>& run_wd = c10::nullopt,
-          const std::vector<double>& run_wd_host = {}) {
+          const std::vector<double>& run_wd_host = {}, const std::vector<int64_t>& sched = {}) {
+  // sched: the learning-rate schedule whose base rate lr is (need_sched; empty = constant)
+  const FdLrSched sc = need_sched(sched, lr, "adam");
   // run_wd: per-run weight decay (device fp32 [nruns], parameter groups) with the same values in
   // run_wd_host, checked here; none = wd for every run
   TORCH_CHECK(std::isfinite(wd) && wd >= 0.0, "adam: weight decay must be finite and >= 0");
@@ -1602,7 +1628,7 @@ void adam(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, const a
   check_rc(fd_adam(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
                    ptr<void>(shadow), n, step.data_ptr<int>(), (float)lr, (float)b1, (float)b2, (float)eps, (float)wd,
                    decoupled ? 1 : 0, ptr<const unsigned char>(touched), ptr<const unsigned char>(now), skip_off,
-                   skip_rows, (int)row_len, rp, nruns, total4, rwd, stream()),
+                   skip_rows, (int)row_len, rp, nruns, total4, rwd, &sc, stream()),
            "adam");
 }
 
@@ -1612,7 +1638,8 @@ void adam(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, const a
 void adam_rows(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, const at::Tensor& v,
                const c10::optional<at::Tensor>& shadow, const at::Tensor& step, double lr, double b1, double b2,
                double eps, const at::Tensor& ever, const c10::optional<at::Tensor>& now, int64_t row_len,
-               double wd = 0.0, bool decoupled = false) {
+               double wd = 0.0, bool decoupled = false, const std::vector<int64_t>& sched = {}) {
+  const FdLrSched sc = need_sched(sched, lr, "adam_rows");
   TORCH_CHECK(std::isfinite(wd) && wd >= 0.0, "adam_rows: weight decay must be finite and >= 0");
   TORCH_CHECK(wd == 0.0 || decoupled, "adam_rows: weight decay needs decoupled decay");
   need(p, at::kFloat, "p");
@@ -1633,7 +1660,7 @@ void adam_rows(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, co
   check_rc(fd_adam_rows(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
                         ptr<void>(shadow), (int)rows, (int)row_len, step.data_ptr<int>(), (float)lr, (float)b1,
                         (float)b2, (float)eps, ever.data_ptr<unsigned char>(), ptr<const unsigned char>(now),
-                        (float)wd, decoupled ? 1 : 0, stream()),
+                        (float)wd, decoupled ? 1 : 0, &sc, stream()),
            "adam_rows");
 }
 
@@ -1643,7 +1670,10 @@ void adam_rows(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, co
 // shadow.  Ids outside the table are ignored by the kernel.
 void adam_lazy_decay(const at::Tensor& p, const c10::optional<at::Tensor>& shadow, const at::Tensor& done,
                      const at::Tensor& ever, const at::Tensor& step, int64_t adj, double lr, double wd,
-                     int64_t row_len, const c10::optional<at::Tensor>& ids) {
+                     int64_t row_len, const c10::optional<at::Tensor>& ids,
+                     const std::vector<int64_t>& sched = {}) {
+  // sched: each missed step's multiplication takes the learning rate of its own step
+  const FdLrSched sc = need_sched(sched, lr, "adam_lazy_decay");
   need(p, at::kFloat, "p");
   need_opt(shadow, at::kBFloat16, "shadow");
   need(done, at::kInt, "done");
@@ -1671,8 +1701,19 @@ void adam_lazy_decay(const at::Tensor& p, const c10::optional<at::Tensor>& shado
   }
   check_rc(fd_adam_lazy_decay(p.data_ptr<float>(), ptr<void>(shadow), done.data_ptr<int>(),
                               ever.data_ptr<unsigned char>(), (int)rows, (int)row_len, step.data_ptr<int>(), (int)adj,
-                              (float)lr, (float)wd, idp, ids64, nids, stream()),
+                              (float)lr, (float)wd, idp, ids64, nids, &sc, stream()),
            "adam_lazy_decay");
+}
+
+// out[i] = the learning rate of optimizer step i + 1 under sched with base rate lr, evaluated by the
+// device function every Adam launch uses (adam_common.h adam_lr_at).
+void lr_schedule_table(const at::Tensor& out, double lr, const std::vector<int64_t>& sched) {
+  need(out, at::kFloat, "out");
+  TORCH_CHECK(out.numel() > 0 && out.numel() < (int64_t(1) << 30), "lr_schedule_table: 1 .. 2^30 steps");
+  TORCH_CHECK(sched.size() == 4, "lr_schedule_table: sched is [kind, warmup, total, offset]");
+  const FdLrSched sc = need_sched(sched, lr, "lr_schedule_table");
+  check_rc(fd_lr_schedule_table(out.data_ptr<float>(), (int)out.numel(), (float)lr, &sc, stream()),
+           "lr_schedule_table");
 }
 
 void step_inc(const c10::optional<at::Tensor>& step, const c10::optional<at::Tensor>& seed) {
@@ -1724,10 +1765,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_dw", &gemm_dw);
   m.def("adam_rows", &adam_rows, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("shadow"),
         py::arg("step"), py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("ever"), py::arg("now"),
-        py::arg("row_len"), py::arg("wd") = 0.0, py::arg("decoupled") = false);
+        py::arg("row_len"), py::arg("wd") = 0.0, py::arg("decoupled") = false,
+        py::arg("sched") = std::vector<int64_t>{});
   m.def("adam_lazy_decay", &adam_lazy_decay, py::arg("p"), py::arg("shadow"), py::arg("done"), py::arg("ever"),
         py::arg("step"), py::arg("adj"), py::arg("lr"), py::arg("wd"), py::arg("row_len"),
-        py::arg("ids") = py::none());
+        py::arg("ids") = py::none(), py::arg("sched") = std::vector<int64_t>{});
   m.def("gemm_ln", &gemm_ln, py::arg("bwd"), py::arg("A"), py::arg("Bt"), py::arg("C"), py::arg("bias"),
         py::arg("res"), py::arg("gamma"), py::arg("beta"), py::arg("mean"), py::arg("rstd"), py::arg("z"),
         py::arg("dx"), py::arg("colpart"), py::arg("stats"), py::arg("cnt"), py::arg("err"), py::arg("eps"),
@@ -1739,7 +1781,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("biases") = std::vector<at::Tensor>{}, py::arg("rest") = std::vector<at::Tensor>{},
         py::arg("rest_i") = std::vector<int64_t>{}, py::arg("decay") = std::vector<double>{},
         py::arg("bias_decay") = std::vector<double>{}, py::arg("rest_wd") = py::none(),
-        py::arg("rest_wd_host") = std::vector<double>{}, py::arg("word_wd") = 0.0);
+        py::arg("rest_wd_host") = std::vector<double>{}, py::arg("word_wd") = 0.0,
+        py::arg("sched") = std::vector<int64_t>{});
   m.def("gemm_colsum", &gemm_colsum, py::arg("epi"), py::arg("A"), py::arg("B"), py::arg("C"), py::arg("aux"),
         py::arg("res"), py::arg("colsum"), py::arg("aux_out") = py::none(), py::arg("kind") = 0,
         py::arg("prefetch") = py::none());
@@ -1808,6 +1851,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("head_ln_bwd", &head_ln_bwd);
   m.def("eval_metrics", &eval_metrics);
   m.def("adam", &adam);
+  m.def("lr_schedule_table", &lr_schedule_table);
   m.def("step_inc", &step_inc);
   m.def("scale_cast", &scale_cast);
   m.def("axpby", &axpby);

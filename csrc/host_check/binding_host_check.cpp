@@ -36,6 +36,14 @@ void span(const void* p, long long bytes, const char* what) {
   violations.push_back(std::string("out of bounds: ") + what + " (" + std::to_string(bytes) + " B)");
 }
 void opt_span(const void* p, long long bytes, const char* what) { if (p) span(p, bytes, what); }
+// a learning-rate schedule as the kernels take it (adam_common.h adam_lr_at: int32 arithmetic)
+void sched(const FdLrSched* s, const char* what) {
+  if (!s) return;
+  const int lim = 1 << 30;
+  if (s->kind < 0 || s->kind > 2 || s->warmup < 0 || s->total < 0 || s->offset < 0 || s->warmup >= lim ||
+      s->total >= lim || s->offset >= lim || (s->kind == 1 && s->warmup > s->total))
+    violations.push_back(std::string(what) + ": learning-rate schedule out of range");
+}
 }  // namespace hc
 
 // ------------------------------------------------------------------ stub launchers
@@ -113,8 +121,10 @@ int fd_gemm_dw2(const void* A0, const void* B0, float* C0, int M0, int N0, const
 }
 int fd_gemm_dw2_splits(int, int, int, int, int) { return 1; }
 int fd_gemm_dw_batch(int n, const FdDwProb* probs, int K, const int* step, const float* hyper, int cfg,
-                     const FdAdamRest* rest, hipStream_t) {
+                     const FdAdamRest* rest, const FdLrSched* sched, hipStream_t) {
   ++hc::calls;
+  hc::sched(sched, "dw_batch");
+  if (sched && sched->kind != 0 && !hyper) hc::violations.push_back("dw_batch: a schedule without the fused Adam");
   if (rest) {
     if (!hyper || !step) hc::violations.push_back("dw_batch rest without the fused Adam");
     if (rest->runs) hc::span(rest->runs, (long long)rest->nruns * 3 * 8, "dw_batch rest runs");
@@ -153,8 +163,9 @@ int fd_gemm_dw_batch(int n, const FdDwProb* probs, int K, const int* step, const
 }
 int fd_adam_rows(float* p, const float* g, float* m, float* v, void* shadow, int rows, int row_len, const int* step,
                  float, float, float, float, const unsigned char* ever, const unsigned char* now, float wd,
-                 int decoupled, hipStream_t) {
+                 int decoupled, const FdLrSched* sched, hipStream_t) {
   ++hc::calls;
+  hc::sched(sched, "adam_rows");
   if (wd != 0.f && !decoupled) hc::violations.push_back("adam_rows: coupled weight decay on flagged rows");
   const long long n = (long long)rows * row_len;
   hc::span(p, n * 4, "adam_rows p");
@@ -169,8 +180,9 @@ int fd_adam_rows(float* p, const float* g, float* m, float* v, void* shadow, int
 }
 int fd_adam_lazy_decay(float* p, void* shadow, int* done, const unsigned char* ever, int rows, int row_len,
                        const int* step, int adj, float, float wd, const void* ids, int ids64, long long n,
-                       hipStream_t) {
+                       const FdLrSched* sched, hipStream_t) {
   ++hc::calls;
+  hc::sched(sched, "lazy decay");
   const long long tot = (long long)rows * row_len;
   hc::span(p, tot * 4, "lazy decay p");
   hc::opt_span(shadow, tot * 2, "lazy decay shadow");
@@ -586,8 +598,9 @@ int fd_eval_metrics(const float*, const long long*, int, double*, long long*, fl
 int fd_adam(float* p, const float* g, float* m, float* v, void* shadow, long long n, const int* step, float, float,
             float, float, float, int, const unsigned char* touched, const unsigned char* now, long long skip_off,
             long long skip_rows, int row_len, const long long* runs, int nruns, long long run_total4,
-            const float* run_wd, hipStream_t) {
+            const float* run_wd, const FdLrSched* sched, hipStream_t) {
   ++hc::calls;
+  hc::sched(sched, "adam");
   if (run_wd) {
     if (!runs) hc::violations.push_back("adam: run decays without a run table");
     hc::span(run_wd, (long long)nruns * 4, "adam run decays");
@@ -614,6 +627,14 @@ int fd_adam(float* p, const float* g, float* m, float* v, void* shadow, long lon
     }
     if (pre != run_total4) hc::violations.push_back("adam: run total");
   }
+  return 0;
+}
+int fd_lr_schedule_table(float* out, int n, float lr, const FdLrSched* sched, hipStream_t) {
+  ++hc::calls;
+  hc::sched(sched, "lr table");
+  if (!sched) hc::violations.push_back("lr table: no schedule");
+  if (!std::isfinite(lr)) hc::violations.push_back("lr table: lr");
+  hc::span(out, (long long)n * 4, "lr table out");
   return 0;
 }
 int fd_step(int*, uint32_t*, hipStream_t) { ++hc::calls; return 0; }
@@ -771,6 +792,16 @@ int main() {
     }
     auto Bbad = Bs;
     Bbad[2] = T_({2000, 768}, bf);
+    expect_ok("dw_batch sched", [&] { gemm_dw_batch(As, Bs, Cs, acc, st, hpw, -1, {}, {}, {}, {}, {}, none, {}, 0.0,
+                                                    {1, 3, 10, 0}); });
+    expect_reject("dw_batch sched kind", [&] { gemm_dw_batch(As, Bs, Cs, acc, st, hpw, -1, {}, {}, {}, {}, {}, none, {},
+                                                             0.0, {3, 3, 10, 0}); });
+    expect_reject("dw_batch sched warmup > total", [&] { gemm_dw_batch(As, Bs, Cs, acc, st, hpw, -1, {}, {}, {}, {}, {},
+                                                                       none, {}, 0.0, {1, 11, 10, 0}); });
+    expect_reject("dw_batch sched without adam", [&] { gemm_dw_batch(As, Bs, Cs, acc, {}, {}, -1, {}, {}, {}, {}, {},
+                                                                     none, {}, 0.0, {1, 3, 10, 0}); });
+    expect_reject("dw_batch lr inf", [&] { gemm_dw_batch(As, Bs, Cs, acc, st, {INFINITY, 0.9, 0.999, 1e-8, 0.0, 0.0},
+                                                         -1); });
     expect_reject("dw_batch K mismatch", [&] { gemm_dw_batch(As, Bbad, Cs, acc, {}, {}, -1); });
     // per-problem rows (the pruned last block: padded [CLS] rows)
     auto Amix = As, Bmix = Bs;
@@ -998,6 +1029,38 @@ int main() {
     expect_reject("lazy decay adj", [&] { adam_lazy_decay(p, sh, done, ever, step, 2, 2e-5, 0.01, 64, none); });
     expect_reject("lazy decay negative", [&] { adam_lazy_decay(p, sh, done, ever, step, 0, 2e-5, -0.01, 64, none); });
     expect_reject("lazy decay ids dtype", [&] { adam_lazy_decay(p, sh, done, ever, step, 0, 2e-5, 0.01, 64, g); });
+    // learning-rate schedules [kind, warmup, total, offset] on every Adam entry point
+    const std::vector<int64_t> lin = {1, 3, 10, 0}, cww = {2, 3, 0, 7}, edge = {1, 5, 5, 0}, cst = {0, 0, 0, 0};
+    const std::vector<std::vector<int64_t>> bad = {{3, 0, 10, 0},  {-1, 0, 10, 0}, {1, -1, 10, 0}, {1, 2, -10, 0},
+                                                   {1, 2, 10, -1}, {1, 11, 10, 0}, {1, 3, 10},     {1, 0, int64_t(1) << 31, 0}};
+    for (const auto& sc : {lin, cww, edge, cst}) {
+      expect_ok("adam sched", [&] { adam(p, g, m, v, sh, step, 2e-5, 0.9, 0.999, 1e-8, 0.01, true, none, none, 0, 0, 4,
+                                         runs, 320, 768, rwd, {0.01, 0.0}, sc); });
+      expect_ok("adam rows sched", [&] { adam_rows(p, g, m, v, sh, step, 2e-5, 0.9, 0.999, 1e-8, ever, now, 64, 0.01,
+                                                   true, sc); });
+      expect_ok("lazy decay sched", [&] { adam_lazy_decay(p, sh, done, ever, step, 1, 2e-5, 0.01, 64, ids, sc); });
+      auto tab = T_({12}, f32);
+      expect_ok("lr table", [&] { lr_schedule_table(tab, 2e-5, sc); });
+    }
+    for (const auto& sc : bad) {
+      expect_reject("adam sched bad", [&] { adam(p, g, m, v, sh, step, 2e-5, 0.9, 0.999, 1e-8, 0, false, none, none, 0, 0,
+                                                 4, runs, 320, 768, none, {}, sc); });
+      expect_reject("adam rows sched bad", [&] { adam_rows(p, g, m, v, sh, step, 2e-5, 0.9, 0.999, 1e-8, ever, now, 64,
+                                                           0.0, false, sc); });
+      expect_reject("lazy decay sched bad", [&] { adam_lazy_decay(p, sh, done, ever, step, 0, 2e-5, 0.01, 64, none, sc); });
+      auto tab = T_({12}, f32);
+      expect_reject("lr table sched bad", [&] { lr_schedule_table(tab, 2e-5, sc); });
+    }
+    // (warmup > total is fine for the constant-with-warmup kind, whose total is unused)
+    expect_ok("adam rows sched warmup only", [&] { adam_rows(p, g, m, v, sh, step, 2e-5, 0.9, 0.999, 1e-8, ever, now, 64,
+                                                             0.0, false, {2, 11, 10, 0}); });
+    expect_reject("adam lr inf", [&] { adam(p, g, m, v, sh, step, INFINITY, 0.9, 0.999, 1e-8, 0, false, none, none, 0, 0,
+                                            4, runs, 320, 768, none, {}, lin); });
+    expect_reject("adam rows lr NaN", [&] { adam_rows(p, g, m, v, sh, step, std::nan(""), 0.9, 0.999, 1e-8, ever, now,
+                                                      64); });
+    expect_reject("lr table lr NaN", [&] { lr_schedule_table(T_({4}, f32), std::nan(""), lin); });
+    expect_reject("lr table empty", [&] { lr_schedule_table(T_({0}, f32), 2e-5, lin); });
+    expect_reject("lr table no schedule", [&] { lr_schedule_table(T_({4}, f32), 2e-5, {}); });
   }
   // ---- embedding backward (work = pieces + LayerNorm partials)
   {

@@ -28,12 +28,37 @@ DEV void adam_decay(float lr, float wd, float& p) {
   p *= 1.f - lr * wd;
 }
 
+// The learning rate of optimizer step `step` (1-based: step[0] after the step's increment) under
+// schedule s with base rate lr (FdLrSched, adam_epi.h; torch / HF get_linear_schedule_with_warmup
+// semantics: the first step of a warmup runs at 0).  ONE copy, contraction off: every launch that
+// evaluates it -- and the lazy decay's catch-up of earlier steps -- gets the same bits.  The
+// constant kind returns lr untouched.
+DEV float adam_lr_at(float lr, FdLrSched s, int step) {
+#pragma clang fp contract(off)
+  // (selects, no branches: one quotient either way, and lr itself wherever the schedule is flat)
+  const int k = s.offset + step - 1;
+  const bool warm = k < s.warmup;
+  const int num = warm ? k : max(0, s.total - k);
+  const int den = warm ? max(1, s.warmup) : max(1, s.total - s.warmup);
+  const float ramp = lr * ((float)num / (float)den);
+  return (s.kind == 0 || (s.kind == 2 && !warm)) ? lr : ramp;
+}
+
+// (lr: this step's learning rate)
 DEV void adam_bias_corr(const int* step, float lr, float b1, float b2, float& step_size, float& inv_sqrt_bc2) {
   const int t = step[0];
   const float bc1 = 1.f - powf(b1, (float)t);
   const float bc2 = 1.f - powf(b2, (float)t);
   step_size = lr / bc1;
   inv_sqrt_bc2 = 1.f / sqrtf(bc2);
+}
+
+// The same under a schedule with base rate lr; lr_t: this step's learning rate (adam_lr_at) -- both
+// step_size and the decoupled decay use it.
+DEV void adam_bias_corr(const int* step, float lr, const FdLrSched& sched, float b1, float b2, float& lr_t,
+                        float& step_size, float& inv_sqrt_bc2) {
+  lr_t = adam_lr_at(lr, sched, step[0]);
+  adam_bias_corr(step, lr_t, b1, b2, step_size, inv_sqrt_bc2);
 }
 
 struct AdamArgs {
@@ -58,6 +83,9 @@ struct AdamArgs {
   // Per-run weight decay, parallel to the run table (nullable = wd for every run): parameter
   // groups -- biases and LayerNorm affines usually decay by 0 (engine/optim.py no_decay).
   const float* run_wd;
+  // lr is the base rate of this schedule; a kernel replaces lr by the step's rate (adam_bias_corr)
+  // before the element loops
+  FdLrSched sched;
 };
 
 // virtual index -> arena float4 index through the run table (binary search on the prefix)

@@ -7,13 +7,20 @@
 #pragma once
 #include <stdint.h>
 
+// Learning-rate schedule, evaluated on the device from the optimizer's step counter
+// (adam_common.h adam_lr_at): the rate of optimizer step t (1-based) is a function of
+// k = offset + t - 1.  kind 0: constant; 1: linear warmup over `warmup` steps, then linear decay to
+// 0 at `total`; 2: the same warmup, then constant.  By value in every Adam launch, so a captured
+// graph replays the whole ramp.
+struct FdLrSched { int kind; int warmup; int total; int offset; };   // kind 0 = constant
+
 struct FdAdamEpi {
   float* p;           // fp32 master (nullptr = no fused optimizer)
   float* m;           // first moment
   float* v;           // second moment
   uint16_t* sh;       // bf16 compute shadow (nullable)
   const int* step;    // device step counter (already advanced for this step)
-  float lr, b1, b2, eps, wd;
+  float lr, b1, b2, eps, wd;   // lr: this step's rate (a schedule is resolved by whoever fills this in)
   int decoupled;      // AdamW-style decay
 };
 

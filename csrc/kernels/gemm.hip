@@ -1784,6 +1784,7 @@ struct DwBatch {
   const int* step;
   float lr, b1, b2, eps, wd;
   int decoupled;
+  FdLrSched sched;  // lr is its base rate (adam_common.h adam_lr_at)
   FdAdamRest rest;  // rest.p != nullptr: blocks [ntiles, ntiles + rest blocks) finish the optimizer step
   // Mixed schedule (fd_gemm_dw_batch plan_dwb_mix; mixed != 0): problems are ordered in three classes
   // -- [long 256 x 256 | long 256 x 128 (half) | short-K 256 x 256] -- and each class is dealt to the
@@ -1820,6 +1821,12 @@ DEV void dwb_tile(const DwBatch& bt, int lid, char* smem) {
     p.adam.p = q.p; p.adam.m = q.m; p.adam.v = q.v; p.adam.sh = q.sh; p.adam.step = bt.step;
     p.adam.lr = bt.lr; p.adam.b1 = bt.b1; p.adam.b2 = bt.b2; p.adam.eps = bt.eps; p.adam.wd = q.wd;
     p.adam.decoupled = bt.decoupled;
+    // A scheduled rate is resolved here, once per thread and outside the K loop (uniform: kept in a
+    // scalar register), so the epilogues -- shared with the launches that take a plain rate -- read
+    // this step's rate from p.adam.lr.  The constant schedule leaves the rate as it came.
+    if (bt.sched.kind != 0)
+      p.adam.lr = __int_as_float(
+          __builtin_amdgcn_readfirstlane(__float_as_int(adam_lr_at(bt.lr, bt.sched, bt.step[0]))));
     if (q.bias && bt.rest.p) {  // the qkv bias's state lies at its gradient's arena offset
       const ptrdiff_t off = q.bias - bt.rest.g;
       p.acol_p = bt.rest.p + off; p.acol_m = bt.rest.m + off; p.acol_v = bt.rest.v + off;
@@ -1858,10 +1865,10 @@ constexpr int DWB_RUNS_LDS = 4096;  // run-table entries (3 per run) staged in L
 template <int NT>
 DEV void dwb_rest(const DwBatch& bt, int rb, char* smem) {
   const FdAdamRest& r = bt.rest;
-  float ss, inv;
-  adam_bias_corr(bt.step, bt.lr, bt.b1, bt.b2, ss, inv);
+  float lr_t, ss, inv;
+  adam_bias_corr(bt.step, bt.lr, bt.sched, bt.b1, bt.b2, lr_t, ss, inv);
   AdamArgs a{};
-  a.step = bt.step; a.lr = bt.lr; a.b1 = bt.b1; a.b2 = bt.b2; a.eps = bt.eps;
+  a.step = bt.step; a.lr = lr_t; a.b1 = bt.b1; a.b2 = bt.b2; a.eps = bt.eps;
   if (rb < r.flat_blocks) {
     a.p = r.p; a.g = r.g; a.m = r.m; a.v = r.v; a.shadow = reinterpret_cast<bf16_t*>(r.sh);
     a.wd = bt.wd; a.decoupled = bt.decoupled;
@@ -2659,7 +2666,7 @@ bool plan_dwb_mix(DwBatch& bt, int mode) {
 }
 
 int fd_gemm_dw_batch(int n, const DwProb* probs, int K, const int* step, const float* hyper, int cfg,
-                     const FdAdamRest* rest, hipStream_t st) {
+                     const FdAdamRest* rest, const FdLrSched* sched, hipStream_t st) {
   if (n <= 0 || n > DWB_MAXP || K <= 0 || K % BKT) return 1;
   DwBatch bt{};
   if (rest && rest->p) {
@@ -2694,6 +2701,7 @@ int fd_gemm_dw_batch(int n, const DwProb* probs, int K, const int* step, const f
     bt.step = step;
     bt.lr = hyper[0]; bt.b1 = hyper[1]; bt.b2 = hyper[2]; bt.eps = hyper[3]; bt.wd = hyper[4];
     bt.decoupled = hyper[5] != 0.f;
+    if (sched) bt.sched = *sched;  // (hyper[0]: its base rate)
   }
   int id = cfg;
   if (id < 0) {

@@ -170,12 +170,14 @@ __global__ __launch_bounds__(256) void eval_metrics_kernel(const float* logits, 
   }
 }
 
+#include "adam_epi.h"
 #include "adam_common.h"
 
 template <bool NT, bool NTP = false>
 __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a) {
-  float step_size, inv_sqrt_bc2;
-  adam_bias_corr(a.step, a.lr, a.b1, a.b2, step_size, inv_sqrt_bc2);
+  float lr_t, step_size, inv_sqrt_bc2;
+  adam_bias_corr(a.step, a.lr, a.sched, a.b1, a.b2, lr_t, step_size, inv_sqrt_bc2);
+  a.lr = lr_t;
   for (long long vi = blockIdx.x * 256ll + threadIdx.x; vi < a.n4; vi += (long long)gridDim.x * 256)
     adam_flat4<NT, NTP>(a, vi, step_size, inv_sqrt_bc2);
 }
@@ -190,8 +192,9 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a) {
 __global__ __launch_bounds__(256) void adam_rows_kernel(AdamArgs a, int rows, int row4) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= rows || !a.touched[row]) return;  // wave-uniform
-  float step_size, inv_sqrt_bc2;
-  adam_bias_corr(a.step, a.lr, a.b1, a.b2, step_size, inv_sqrt_bc2);
+  float lr_t, step_size, inv_sqrt_bc2;
+  adam_bias_corr(a.step, a.lr, a.sched, a.b1, a.b2, lr_t, step_size, inv_sqrt_bc2);
+  a.lr = lr_t;
   if (row4 == 192) adam_row768(a, row, lane, step_size, inv_sqrt_bc2);
   else adam_row(a, 0, row, row4, lane, step_size, inv_sqrt_bc2);
 }
@@ -201,8 +204,9 @@ __global__ __launch_bounds__(256) void adam_rows_kernel(AdamArgs a, int rows, in
 // counts the steps whose multiplication the row has received.  One wave per entry of ids (the
 // rows a forward is about to gather; nullable = every row of the table): it raises done[row] to
 // the number of completed steps (step[0] - adj) with an atomic -- duplicate ids: one wave wins --
-// and applies the missing multiplications one by one (adam_decay: bitwise the dense launches),
-// writing the master and the bf16 shadow.
+// and applies the missing multiplications one by one in step order, each with the learning rate
+// of its own step (adam_lr_at; adam_decay: bitwise the dense launches), writing the master and the
+// bf16 shadow.
 struct LazyDecayArgs {
   float* p;
   bf16_t* shadow;  // nullable
@@ -211,6 +215,7 @@ struct LazyDecayArgs {
   const int* step;
   int adj;
   float lr, wd;
+  FdLrSched sched;  // lr is its base rate
   int rows, row4;
   const void* ids;  // nullable
   int ids64;
@@ -232,15 +237,23 @@ __global__ __launch_bounds__(256) void adam_lazy_decay_kernel(LazyDecayArgs a) {
   for (int c = lane; c < a.row4; c += 64) {
     const long long i = row * a.row4 + c;
     float4 p = reinterpret_cast<const float4*>(a.p)[i];
-    for (int s = 0; s < k; ++s) {
-      adam_decay(a.lr, a.wd, p.x);
-      adam_decay(a.lr, a.wd, p.y);
-      adam_decay(a.lr, a.wd, p.z);
-      adam_decay(a.lr, a.wd, p.w);
+    for (int s = old + 1; s <= target; ++s) {
+      const float lr_s = adam_lr_at(a.lr, a.sched, s);
+      adam_decay(lr_s, a.wd, p.x);
+      adam_decay(lr_s, a.wd, p.y);
+      adam_decay(lr_s, a.wd, p.z);
+      adam_decay(lr_s, a.wd, p.w);
     }
     reinterpret_cast<float4*>(a.p)[i] = p;
     if (a.shadow) reinterpret_cast<uint2*>(a.shadow)[i] = make_uint2(pack_bf2(p.x, p.y), pack_bf2(p.z, p.w));
   }
+}
+
+// out[i] = the learning rate of step i + 1 (adam_lr_at): the device's own numbers, for tests and
+// logs.
+__global__ __launch_bounds__(256) void lr_table_kernel(float* out, int n, float lr, FdLrSched sched) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = adam_lr_at(lr, sched, i + 1);
 }
 
 __global__ void step_kernel(int* step, uint32_t* seed) {
@@ -329,7 +342,7 @@ int fd_eval_metrics(const float* logits, const long long* labels, int B, double*
 int fd_adam(float* p, const float* g, float* m, float* v, void* shadow, long long n, const int* step, float lr,
             float b1, float b2, float eps, float wd, int decoupled, const unsigned char* touched,
             const unsigned char* now, long long skip_off, long long skip_rows, int row_len, const long long* runs,
-            int nruns, long long run_total4, const float* run_wd, hipStream_t st) {
+            int nruns, long long run_total4, const float* run_wd, const FdLrSched* sched, hipStream_t st) {
   if (n % 4 != 0 || skip_off % 4 != 0 || row_len % 4 != 0) return 1;
   // skipping untouched rows is exact without weight decay; with decoupled decay the caller owes
   // those rows their multiplications (fd_adam_lazy_decay)
@@ -337,7 +350,8 @@ int fd_adam(float* p, const float* g, float* m, float* v, void* shadow, long lon
   if (run_wd && (touched || !runs)) return 5;
   if (runs && (nruns <= 0 || run_total4 <= 0)) return 4;
   AdamArgs a{p, g, m, v, (bf16_t*)shadow, runs ? run_total4 : n / 4, step, lr, b1, b2, eps, wd, decoupled,
-             skip_off / 4, (skip_off + skip_rows * row_len) / 4, row_len / 4, touched, now, runs, nruns, run_wd};
+             skip_off / 4, (skip_off + skip_rows * row_len) / 4, row_len / 4, touched, now, runs, nruns, run_wd,
+             sched ? *sched : FdLrSched{}};
   const int grid = grid_for(n / 4);
   // FD_ADAM_NT: 0 = default cache policy, 1 = nontemporal g/m/v, 2 = also the fp32 master (default:
   // 2.336 vs 2.366-2.387 ms/step, profiles/r1_ab_adam_nt_master.txt -- only the bf16 shadow is re-read soon)
@@ -355,11 +369,11 @@ int fd_adam(float* p, const float* g, float* m, float* v, void* shadow, long lon
 // decoupled: the unflagged rows' decay is applied lazily, fd_adam_lazy_decay).
 int fd_adam_rows(float* p, const float* g, float* m, float* v, void* shadow, int rows, int row_len, const int* step,
                  float lr, float b1, float b2, float eps, const unsigned char* ever, const unsigned char* now,
-                 float wd, int decoupled, hipStream_t st) {
+                 float wd, int decoupled, const FdLrSched* sched, hipStream_t st) {
   if (row_len % 4 != 0 || rows <= 0 || !ever) return 1;
   if (wd != 0.f && !decoupled) return 3;
   AdamArgs a{p, g, m, v, (bf16_t*)shadow, 0, step, lr, b1, b2, eps, wd, decoupled, 0, 0, row_len / 4, ever, now,
-             nullptr, 0, nullptr};
+             nullptr, 0, nullptr, sched ? *sched : FdLrSched{}};
   hipLaunchKernelGGL(adam_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, a, rows, row_len / 4);  // wave per row
   return 0;
 }
@@ -368,12 +382,18 @@ int fd_adam_rows(float* p, const float* g, float* m, float* v, void* shadow, int
 // (adam_lazy_decay_kernel): the rows named by the n entries of ids, or every row (ids == nullptr).
 int fd_adam_lazy_decay(float* p, void* shadow, int* done, const unsigned char* ever, int rows, int row_len,
                        const int* step, int adj, float lr, float wd, const void* ids, int ids64, long long n,
-                       hipStream_t st) {
+                       const FdLrSched* sched, hipStream_t st) {
   if (row_len % 4 != 0 || rows <= 0 || !p || !done || !ever || !step || adj < 0) return 1;
   if (ids && (n <= 0 || n > (1ll << 30))) return 2;
-  LazyDecayArgs a{p, (bf16_t*)shadow, done, ever, step, adj, lr, wd, rows, row_len / 4, ids, ids64,
-                  ids ? (int)n : rows};
+  LazyDecayArgs a{p, (bf16_t*)shadow, done, ever, step, adj, lr, wd, sched ? *sched : FdLrSched{}, rows, row_len / 4,
+                  ids, ids64, ids ? (int)n : rows};
   hipLaunchKernelGGL(adam_lazy_decay_kernel, dim3((a.n + 3) / 4), dim3(256), 0, st, a);
+  return 0;
+}
+
+int fd_lr_schedule_table(float* out, int n, float lr, const FdLrSched* sched, hipStream_t st) {
+  if (!out || n <= 0 || !sched) return 1;
+  hipLaunchKernelGGL(lr_table_kernel, dim3((n + 255) / 256), dim3(256), 0, st, out, n, lr, *sched);
   return 0;
 }
 

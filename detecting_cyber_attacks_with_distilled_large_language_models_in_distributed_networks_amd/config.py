@@ -44,6 +44,14 @@ class FedConfig:
     weight_decay: float = 0.0
     decoupled_weight_decay: bool = False    # AdamW when True
     no_decay: str = ""                      # comma-separated name substrings excluded from weight decay
+    # learning-rate schedule (engine/optim.py): "constant" | "linear" (warmup, then linear decay to 0:
+    # HF get_linear_schedule_with_warmup) | "constant_with_warmup"
+    lr_schedule: str = "constant"
+    warmup_ratio: float = 0.0               # warmup as a share of the schedule's steps
+    warmup_steps: int = 0                   # wins over warmup_ratio when > 0
+    # "round": every round's fresh Adam restarts the ramp over that round's steps;
+    # "run": one ramp over rounds x steps per round (round r starts at offset r x steps per round)
+    lr_schedule_scope: str = "round"
     impl: str = "auto"                      # "hip" | "torch" | "auto" (hip on GPU)
     use_graph: bool = True                  # capture the train step in a HIP graph
     # --- federation (server.py:10-13) -------------------------------------------------

@@ -76,6 +76,19 @@ The sparse word-embedding table under weight decay:
 3. coupled (L2) decay, word table decays: the gradient ``wd * p`` is non-zero for every row, so
    nothing can be skipped -- the dense word gradient and the dense table update, as before.
 
+Learning-rate schedules.  ``schedule="linear"`` is HF ``get_linear_schedule_with_warmup`` (the rate
+rises from 0 over ``warmup_steps`` steps, then falls to 0 at ``total_steps``; the first step of a
+warmup runs at exactly 0), ``"constant_with_warmup"`` the same ramp and then the base rate.  The
+rate of optimizer step t is a formula of ``k = step_offset + t - 1`` that every Adam launch
+evaluates on the device from the step counter it already reads (csrc/kernels/adam_common.h
+adam_lr_at), so a captured graph -- which holds ``lr`` and the schedule by value -- replays the
+whole ramp, and the lazy word-row decay multiplies a row by ``1 - lr_at(s) * wd`` for each missed
+step s in order.  ``lr_at(step)`` is the host mirror (float32 arithmetic), used by the CPU path.
+``total_steps == 0`` on a non-constant schedule means "resolved by the training loop"
+(``train_model`` fills in epochs x batches); ``set_schedule`` changes the numbers only before the
+optimizer's first step (or after ``reset_state()``), because captured graphs keep the old ones.
+With the default ``schedule="constant"`` nothing changes, bit for bit.
+
 Data-parallel replicas (parallel/dp.py) exchange row flags, which the lazy decay does not cover:
 ``make_dp_step_fn`` switches a decaying word table to the dense path (``dense_word_decay()``).
 """
@@ -85,15 +98,47 @@ import math
 import weakref
 from typing import Optional
 
+import numpy as np
 import torch
+
+# schedule name -> FdLrSched::kind (csrc/kernels/adam_epi.h)
+SCHEDULES = {"constant": 0, "linear": 1, "constant_with_warmup": 2}
+
+
+def check_schedule(schedule: str, warmup_steps: int, total_steps: int, step_offset: int = 0):
+    """Raise ValueError unless the numbers describe a schedule the kernels take (total_steps == 0:
+    not resolved yet, see ``ArenaAdam``)."""
+    if schedule not in SCHEDULES:
+        raise ValueError(f"unknown lr schedule {schedule!r} (one of {', '.join(SCHEDULES)})")
+    for name, val in (("warmup_steps", warmup_steps), ("total_steps", total_steps), ("step_offset", step_offset)):
+        if int(val) != val or not 0 <= val < 2 ** 30:
+            raise ValueError(f"{name} must be an integer in [0, 2^30), got {val}")
+    if schedule == "linear" and total_steps > 0 and warmup_steps > total_steps:
+        raise ValueError(f"linear schedule: warmup_steps ({warmup_steps}) > total_steps ({total_steps})")
+
+
+class FusedHyper(list):
+    """``fused_args``'s hyper-parameters [lr, b1, b2, eps, wd, decoupled] with the schedule that lr is
+    the base rate of (``sched``: None, or the launches' (kind, warmup, total, offset))."""
+    sched = None
 
 
 class ArenaAdam:
     def __init__(self, model, lr: float = 2e-5, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, decoupled: bool = False, overlap: bool = False,
-                 fuse_dw: bool = True, no_decay=()):
+                 fuse_dw: bool = True, no_decay=(), schedule: str = "constant", warmup_steps: int = 0,
+                 total_steps: int = 0, step_offset: int = 0, warmup_ratio: float = 0.0):
         if not (math.isfinite(weight_decay) and weight_decay >= 0.0):
             raise ValueError(f"weight_decay must be finite and >= 0, got {weight_decay}")
+        if not math.isfinite(lr):
+            raise ValueError(f"lr must be finite, got {lr}")
+        if not 0.0 <= warmup_ratio <= 1.0:
+            raise ValueError(f"warmup_ratio must lie in [0, 1], got {warmup_ratio}")
+        check_schedule(schedule, warmup_steps, total_steps, step_offset)
+        self.schedule = schedule
+        # warmup_ratio: the warmup as a share of total_steps, used while warmup_steps == 0
+        self.warmup_steps, self.warmup_ratio = int(warmup_steps), float(warmup_ratio)
+        self.total_steps, self.step_offset = int(total_steps), int(step_offset)
         if isinstance(no_decay, str):
             no_decay = no_decay.split(",")
         self.model = model
@@ -119,6 +164,55 @@ class ArenaAdam:
             if not getattr(model, "_lazy_decay_hook", False) and hasattr(model, "register_state_dict_pre_hook"):
                 model.register_state_dict_pre_hook(_flush_before_state_dict)
                 model._lazy_decay_hook = True
+
+    # -------------------------------------------------------------- learning-rate schedule
+    def schedule_unresolved(self) -> bool:
+        """A non-constant schedule whose total the training loop has yet to fill in."""
+        return self.schedule != "constant" and self.total_steps == 0
+
+    def _warmup(self) -> int:
+        if self.warmup_steps > 0 or self.warmup_ratio <= 0.0:
+            return self.warmup_steps
+        return min(self.total_steps, int(math.ceil(self.total_steps * self.warmup_ratio)))
+
+    def set_schedule(self, total_steps=None, warmup_steps=None, step_offset=None):
+        """Change the schedule's numbers.  Only before the optimizer's first step since its creation
+        or the last ``reset_state()``: captured graphs hold the schedule by value."""
+        if self._begun:
+            raise RuntimeError("set_schedule inside a step")
+        if self.host_step > 0:
+            raise RuntimeError("set_schedule after the optimizer has taken a step: captured graphs hold the "
+                               "schedule by value (reset_state() first)")
+        new = (self.warmup_steps if warmup_steps is None else warmup_steps,
+               self.total_steps if total_steps is None else total_steps,
+               self.step_offset if step_offset is None else step_offset)
+        check_schedule(self.schedule, *new)
+        self.warmup_steps, self.total_steps, self.step_offset = (int(x) for x in new)
+
+    def sched_args(self):
+        """The ``sched=`` argument of the Adam launches: None (constant) or (kind, warmup, total,
+        offset) with ``lr`` as the base rate."""
+        if self.schedule == "constant":
+            return None
+        if self.total_steps == 0:
+            raise RuntimeError(f"lr schedule {self.schedule!r}: total_steps is not set (train_model fills it in; "
+                               "a hand-written loop calls set_schedule(total_steps=...))")
+        return (SCHEDULES[self.schedule], self._warmup(), self.total_steps, self.step_offset)
+
+    def lr_at(self, step: int) -> float:
+        """The learning rate of optimizer step ``step`` (1-based): the host mirror of the device
+        function (csrc/kernels/adam_common.h adam_lr_at), the same formula in float32 arithmetic."""
+        sc = self.sched_args()
+        if sc is None:
+            return self.lr
+        _, warmup, total, offset = sc
+        f32 = np.float32
+        k = offset + int(step) - 1
+        if k < warmup:
+            return float(f32(self.lr) * (f32(k) / f32(max(1, warmup))))
+        if self.schedule == "constant_with_warmup":
+            return float(f32(self.lr))
+        return float(f32(self.lr) * (f32(max(0, total - k)) / f32(max(1, total - warmup))))
 
     # -------------------------------------------------------------- parameter groups
     def _build_groups(self):
@@ -205,7 +299,8 @@ class ArenaAdam:
         p, sh, rl = self._word_views()
         # (inside a step the counter already counts the running one)
         K.adam_lazy_decay(p, sh, self.row_step, self.model.emb_ever, self.step_t, 1 if self._begun else 0,
-                          self.lr, self.word_wd, rl, ids if ids.is_contiguous() else ids.contiguous())
+                          self.lr, self.word_wd, rl, ids if ids.is_contiguous() else ids.contiguous(),
+                          sched=self.sched_args())
 
     def finish(self):
         """Settle the lazy decay: every word row without Adam state is brought up to the current
@@ -218,7 +313,7 @@ class ArenaAdam:
         from ..ops import kernels as K
         p, sh, rl = self._word_views()
         K.adam_lazy_decay(p, sh, self.row_step, self.model.emb_ever, self.step_t, 1 if self._begun else 0,
-                          self.lr, self.word_wd, rl, None)
+                          self.lr, self.word_wd, rl, None, sched=self.sched_args())
         self.model.mark_shadow_synced()
         self._lazy_pending = self._begun
 
@@ -278,10 +373,10 @@ class ArenaAdam:
             woff, rows, rl = self.model.word_embedding_span()
             K.adam(A.master[sl], A.grad[sl], self.m[sl], self.v[sl], A.shadow[sl], self.step_t, self.lr, b1, b2,
                    self.eps, wd, self.decoupled, self.model.emb_ever, self.model.emb_now, woff - off,
-                   rows, rl)
+                   rows, rl, sched=self.sched_args())
         else:
             K.adam(A.master[sl], A.grad[sl], self.m[sl], self.v[sl], A.shadow[sl], self.step_t, self.lr, b1, b2,
-                   self.eps, wd, self.decoupled)
+                   self.eps, wd, self.decoupled, sched=self.sched_args())
 
     def _on_layer_grads(self, i: int):
         """Backward hook: block i's gradients are final -> update it on the side stream."""
@@ -311,7 +406,9 @@ class ArenaAdam:
 
     def fused_args(self, grads):
         """(state tensors, hyper-parameters) for a weight-gradient GEMM that applies Adam to
-        ``grads`` (arena grad views) in its epilogue; those spans are skipped by ``step()``."""
+        ``grads`` (arena grad views) in its epilogue; those spans are skipped by ``step()``.  The
+        hyper-parameters carry the schedule (``FusedHyper.sched``): the all-layer launch passes it on
+        (ops/kernels.py linear_dw_batch), the per-layer launches, which take none, refuse it."""
         from ..ops import kernels as K  # noqa: F401  (extension must be present)
         self._begin()
         A = self.arena
@@ -326,7 +423,9 @@ class ArenaAdam:
             self._done.append((off, n))
         st.append(self.step_t)
         b1, b2 = self.betas
-        return st, [self.lr, b1, b2, self.eps, self.weight_decay, 1.0 if self.decoupled else 0.0]
+        hp = FusedHyper([self.lr, b1, b2, self.eps, self.weight_decay, 1.0 if self.decoupled else 0.0])
+        hp.sched = self.sched_args()
+        return st, hp
 
     def _runs_table(self, runs):
         """Cached device run table for ``runs`` (built during the eager warm-up steps, so a
@@ -468,6 +567,7 @@ class ArenaAdam:
         if A.master.device != self.m.device:
             self._alloc()
         b1, b2 = self.betas
+        sc = self.sched_args()  # (raises while a schedule's total is unresolved)
         if A.master.is_cuda:
             self._begin()
             if getattr(self, "_rest_in_launch", False):
@@ -492,11 +592,13 @@ class ArenaAdam:
                 wend = woff + rows * rl
                 sl = slice(woff, wend)
                 K.adam_rows(A.master[sl], A.grad[sl], self.m[sl], self.v[sl], A.shadow[sl], self.step_t, self.lr, b1,
-                            b2, self.eps, self.model.emb_ever, self.model.emb_now, rl, self.word_wd, self.decoupled)
+                            b2, self.eps, self.model.emb_ever, self.model.emb_now, rl, self.word_wd, self.decoupled,
+                            sched=sc)
                 rest_table = self._runs_table(rest) if len(rest) > 1 else None
                 if rest_table is not None:
                     K.adam(A.master, A.grad, self.m, self.v, A.shadow, self.step_t, self.lr, b1, b2, self.eps,
-                           self.weight_decay, self.decoupled, runs=rest_table, run_decay=self._runs_decay(rest))
+                           self.weight_decay, self.decoupled, runs=rest_table, run_decay=self._runs_decay(rest),
+                           sched=sc)
                 else:
                     for off, n in rest:
                         self._update(off, n, False)
@@ -504,7 +606,7 @@ class ArenaAdam:
                 from ..ops import kernels as K
                 b1, b2 = self.betas
                 K.adam(A.master, A.grad, self.m, self.v, A.shadow, self.step_t, self.lr, b1, b2, self.eps,
-                       self.weight_decay, self.decoupled, runs=table, run_decay=self._runs_decay(runs))
+                       self.weight_decay, self.decoupled, runs=table, run_decay=self._runs_decay(runs), sched=sc)
             else:
                 for off, n in runs:
                     self._update(off, n, sparse and off <= woff < off + n)
@@ -517,6 +619,7 @@ class ArenaAdam:
         self.host_step += 1
         t = self.host_step
         self.step_t += 1
+        lr = self.lr_at(t)
         p, g = A.master, A.grad
         if self.weight_decay and self.grouped_decay:  # one group per segment, as torch.optim's param groups
             if not self.decoupled:
@@ -525,12 +628,12 @@ class ArenaAdam:
                 if wd == 0.0:
                     continue
                 if self.decoupled:
-                    p[a:b].mul_(1 - self.lr * wd)
+                    p[a:b].mul_(1 - lr * wd)
                 else:
                     g[a:b] += wd * p[a:b]
         elif self.weight_decay:
             if self.decoupled:
-                p.mul_(1 - self.lr * self.weight_decay)
+                p.mul_(1 - lr * self.weight_decay)
             else:
                 g = g + self.weight_decay * p
         self.m.mul_(b1).add_(g, alpha=1 - b1)
@@ -538,17 +641,28 @@ class ArenaAdam:
         bc1 = 1 - b1 ** t
         bc2 = 1 - b2 ** t
         denom = (self.v.sqrt() / math.sqrt(bc2)).add_(self.eps)
-        p.addcdiv_(self.m, denom, value=-self.lr / bc1)
+        p.addcdiv_(self.m, denom, value=-lr / bc1)
         self.model.mark_shadow_synced()
 
     def state_dict(self):
         self.finish()
-        return {"m": self.m.cpu(), "v": self.v.cpu(), "step": int(self.step_t.item()),
-                "lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.weight_decay,
-                "decoupled": self.decoupled}
+        sd = {"m": self.m.cpu(), "v": self.v.cpu(), "step": int(self.step_t.item()),
+              "lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.weight_decay,
+              "decoupled": self.decoupled}
+        if self.schedule != "constant":  # (the constant schedule keeps the dictionary's keys as they were)
+            sd["schedule"] = {"name": self.schedule, "warmup_steps": self.warmup_steps,
+                              "warmup_ratio": self.warmup_ratio, "total_steps": self.total_steps,
+                              "step_offset": self.step_offset}
+        return sd
 
     def load_state_dict(self, sd):
         self.finish()  # (before every row counts as having state)
+        sch = sd.get("schedule")
+        if sch is not None:  # resume at the saved point of the ramp
+            check_schedule(sch["name"], sch["warmup_steps"], sch["total_steps"], sch["step_offset"])
+            self.schedule = sch["name"]
+            self.warmup_steps, self.warmup_ratio = int(sch["warmup_steps"]), float(sch.get("warmup_ratio", 0.0))
+            self.total_steps, self.step_offset = int(sch["total_steps"]), int(sch["step_offset"])
         if getattr(self.model, "emb_ever", None) is not None:
             self.model.emb_ever.fill_(1)  # unknown history: treat every row as having state
         self.m.copy_(sd["m"])

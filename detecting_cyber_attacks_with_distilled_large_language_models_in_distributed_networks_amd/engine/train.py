@@ -143,6 +143,11 @@ def train_model(model, train_loader, criterion=None, optimizer=None, num_epochs:
         fn = make_dp_step_fn(model, optimizer, grad_sync)
     else:
         fn = make_step_fn(model, optimizer, criterion)
+    if getattr(optimizer, "schedule_unresolved", lambda: False)():
+        # a learning-rate schedule left open: it spans this call's steps (the data-parallel shard
+        # loader yields one batch per client step, like the plain one)
+        total = num_epochs * len(train_loader)
+        optimizer.set_schedule(total_steps=total if max_steps is None else min(total, max_steps))
     step = GraphedTrainStep(fn, enabled=use_graph and model.device.type == "cuda",
                             bucket=getattr(model, "packed_rows", None))
     epoch_losses: List[float] = []

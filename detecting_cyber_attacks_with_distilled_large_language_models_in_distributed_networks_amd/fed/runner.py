@@ -37,12 +37,41 @@ from ..utils.metrics import save_metrics
 from ..utils.timers import PhaseTimer
 
 
-def make_optimizer(model, cfg: FedConfig) -> ArenaAdam:
-    """The client optimizer of a run: Adam / AdamW with the configuration's hyper-parameters and
-    its no-decay parameter group (``--no-decay bias,LayerNorm,layer_norm``)."""
+def _schedule_kwargs(cfg: FedConfig, round_index: int = 0, rounds: int = 1,
+                     steps_per_round: Optional[int] = None) -> Dict:
+    """``ArenaAdam``'s schedule keywords for the configuration (``--lr-schedule linear --warmup-ratio
+    0.1``).  Scope "round": the ramp covers one round's steps -- the total is left to ``train_model``
+    (epochs x batches).  Scope "run": one ramp over ``rounds * steps_per_round`` steps, round
+    ``round_index`` starting at offset ``round_index * steps_per_round`` (derived from the round
+    index alone, so a resumed job needs no saved state)."""
+    if cfg.lr_schedule == "constant":
+        return {}
+    if cfg.lr_schedule_scope not in ("round", "run"):
+        raise ValueError(f"lr_schedule_scope must be 'round' or 'run', got {cfg.lr_schedule_scope!r}")
+    kw = {"schedule": cfg.lr_schedule, "warmup_steps": cfg.warmup_steps, "warmup_ratio": cfg.warmup_ratio}
+    if cfg.lr_schedule_scope == "run" and steps_per_round:
+        kw["total_steps"] = int(rounds) * int(steps_per_round)
+        kw["step_offset"] = int(round_index) * int(steps_per_round)
+    return kw
+
+
+def make_optimizer(model, cfg: FedConfig, round_index: int = 0, rounds: int = 1,
+                   steps_per_round: Optional[int] = None) -> ArenaAdam:
+    """The client optimizer of a run: Adam / AdamW with the configuration's hyper-parameters, its
+    no-decay parameter group (``--no-decay bias,LayerNorm,layer_norm``) and its learning-rate
+    schedule (``_schedule_kwargs``; round_index / rounds / steps_per_round matter to scope "run")."""
     return ArenaAdam(model, lr=cfg.lr, betas=cfg.betas, eps=cfg.eps, weight_decay=cfg.weight_decay,
                      decoupled=cfg.decoupled_weight_decay,
-                     no_decay=tuple(x.strip() for x in cfg.no_decay.split(",") if x.strip()))
+                     no_decay=tuple(x.strip() for x in cfg.no_decay.split(",") if x.strip()),
+                     **_schedule_kwargs(cfg, round_index, rounds, steps_per_round))
+
+
+def make_teacher_optimizer(teacher, cfg: FedConfig) -> ArenaAdam:
+    """The teacher's plain Adam; with a configured schedule, the same schedule over the teacher's
+    own step count (``train_model`` fills in the total)."""
+    if cfg.lr_schedule == "constant":
+        return ArenaAdam(teacher, lr=cfg.lr)
+    return ArenaAdam(teacher, lr=cfg.lr, **_schedule_kwargs(cfg))
 
 
 def _metrics_record(m) -> Dict:
@@ -194,7 +223,7 @@ class FederatedClient:
     def run_round(self, r: int) -> Dict:
         cfg, log, model = self.cfg, self.log, self.model
         log.phase(f"Starting round {r + 1}/{cfg.rounds}")
-        opt = make_optimizer(model, cfg)
+        opt = make_optimizer(model, cfg, r, cfg.rounds, cfg.epochs * len(self.train_loader))
         opt.reset_state()  # a fresh Adam every round (client1.py:380), "has state" row flags included
         opt_path = os.path.join(cfg.out_dir, f"client{self.client_id}_optim.pth")
         if cfg.save_optimizer and r == self.start_round:
@@ -203,7 +232,7 @@ class FederatedClient:
         if self.teacher is not None and r == self.start_round:
             # Local teacher fine-tune (BERT-base, same kernels), then distil into the student.
             log.info("training BERT-base teacher")
-            t_opt = ArenaAdam(self.teacher, lr=cfg.lr)
+            t_opt = make_teacher_optimizer(self.teacher, cfg)
             with self.timer("teacher"):
                 train_model(self.teacher, self.train_loader, None, t_opt, int(cfg.extra.get("teacher_epochs", cfg.epochs)),
                             log=log, use_graph=cfg.use_graph and (self.teacher_sync is None or cfg.dp_graph
@@ -460,7 +489,7 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
                     with torch.no_grad():
                         teacher.arena.master.copy_(t_init)
                     teacher.sync_shadow(force=True)
-                    t_opt = ArenaAdam(teacher, lr=cfg.lr)
+                    t_opt = make_teacher_optimizer(teacher, cfg)
                     t_opt.reset_state()
                     teacher.train()
                     rec["teacher_train"] = train_model(
@@ -480,7 +509,7 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
                 model.rng.copy_(c["rng"])
             model.torch_counter = c["torch_counter"]
             model.sync_shadow(force=True)
-            opt = make_optimizer(model, cfg)
+            opt = make_optimizer(model, cfg, r, rounds, cfg.epochs * len(loader))
             opt.reset_state()  # (also clears the sparse word rows' "has Adam state" flags)
             tr = train_model(model, loader, None, opt, cfg.epochs, log=client.log, use_graph=cfg.use_graph,
                              teacher=teacher, kd_temperature=cfg.kd_temperature, kd_alpha=cfg.kd_alpha)

@@ -149,6 +149,14 @@ def linear_dx(dy: torch.Tensor, w: torch.Tensor, gelu_u: Optional[torch.Tensor] 
     return dx
 
 
+def _no_sched(hp, what: str):
+    """The per-layer fused dW launches take a plain rate: refuse a scheduled optimizer's
+    hyper-parameters (``FusedHyper.sched``) instead of training at its base rate."""
+    if getattr(hp, "sched", None) is not None:
+        raise ValueError(f"{what}: the fused Adam of this launch takes no learning-rate schedule "
+                         "(use the all-layer launch, linear_dw_batch)")
+
+
 def linear_dw(dy: torch.Tensor, x: torch.Tensor, out: torch.Tensor, accumulate: bool = False,
               adam=None) -> torch.Tensor:
     """out[N_out, N_in] (fp32) (+)= dy^T x (split-K fp32 slabs + a deterministic reduce launch).
@@ -157,6 +165,7 @@ def linear_dw(dy: torch.Tensor, x: torch.Tensor, out: torch.Tensor, accumulate: 
     M, N = dy.shape[1], x.shape[1]
     ws = workspace(dy.device, "splitk", 8 * M * N)
     st, hp = adam if adam is not None else ([], [])
+    _no_sched(hp, "linear_dw")
     ext().gemm_dw(dy, x, out, ws, accumulate, st, hp)
     return out
 
@@ -176,6 +185,7 @@ def linear_dw2(dy0: torch.Tensor, x0: torch.Tensor, out0: torch.Tensor, dy1: tor
     ws = workspace(dy0.device, f"splitk_def{len(jobs)}", planned * n) if defer else \
         workspace(dy0.device, "splitk", 8 * n)
     st, hp = adam if adam is not None else ([], [])
+    _no_sched(hp, "linear_dw2")
     splits = ext().gemm_dw2(dy0, x0, out0, dy1, x1, out1, ws, accumulate, st, hp, defer)
     if splits:
         s0 = splits * out0.numel()
@@ -198,14 +208,16 @@ ADAM_IN_DW = _os.environ.get("FD_ADAM_IN_DW", "1") != "0"
 DWB_ORDER = int(_os.environ.get("FD_DWB_ORDER", "0"))
 
 
-def linear_dw_batch(jobs: list, adam=None, cfg: int = -1, opt=None):
+def linear_dw_batch(jobs: list, adam=None, cfg: int = -1, opt=None, sched=None):
     """Every weight gradient of a backward in one launch per 32 problems: for each job
     (dy [K, M], x [K, N], out [M, N] fp32, accumulate[, bias]) out (+)= dy^T x, and the
     optional fp32 [M] bias (+)= the column sums of dy (``DW_QKV_BIAS``).  No split-K: each
     output tile runs the whole token dimension (deterministic, no slabs, no reduce).
     adam: a callable grads -> (state, hyper) (``ArenaAdam.fused_args``): apply the optimizer
     step to each finished gradient tile instead of storing it.  opt (with adam): the optimizer
-    (``ArenaAdam``) -- the last launch also runs the rest of its step (``ADAM_IN_DW``)."""
+    (``ArenaAdam``) -- the last launch also runs the rest of its step (``ADAM_IN_DW``).
+    sched (with adam): the learning-rate schedule (kind, warmup, total, offset) whose base rate the
+    hyper-parameters carry; None: the one they name themselves (``FusedHyper.sched``)."""
     if DWB_ORDER == 1 and len(jobs) <= DW_BATCH_MAX:
         jobs = jobs[::-1]  # (forward block order: the pruned block's problems last)
     starts = list(range(0, len(jobs), DW_BATCH_MAX))
@@ -218,6 +230,9 @@ def linear_dw_batch(jobs: list, adam=None, cfg: int = -1, opt=None):
         # parameter groups (ArenaAdam(no_decay=)): each matrix's and each in-launch bias's decay
         groups = opt is not None and adam is not None and getattr(opt, "grouped_decay", False)
         extra = {"decay": opt.decays_of(outs)} if groups else {}
+        sc = sched if sched is not None else getattr(hp, "sched", None)
+        if adam is not None and sc is not None:
+            extra["sched"] = _sched(sc)
         if adam is not None and opt is not None and ADAM_IN_DW and i == starts[-1]:
             # the qkv biases summed by this launch are updated by its tiles when it also finishes
             # the step: mark them, then hand the rest of the step to the launch
@@ -994,32 +1009,52 @@ def eval_metrics(logits, labels, acc, counts, prob1=None, preds=None):
     ext().eval_metrics(logits, labels, acc, counts, prob1, preds)
 
 
+LR_SCHEDULES = {"constant": 0, "linear": 1, "constant_with_warmup": 2}  # FdLrSched::kind (csrc/kernels/adam_epi.h)
+
+
+def _sched(sched):
+    """sched=None (constant) or (kind, warmup, total, offset) -> the binding's int list."""
+    return [] if sched is None else [int(x) for x in sched]
+
+
+def lr_schedule_table(lr, sched, n):
+    """float32 [n] on the current GPU: the learning rate of optimizer steps 1..n under
+    ``sched = (kind, warmup, total, offset)`` with base rate ``lr``, written by the device function
+    every Adam launch evaluates (csrc/kernels/adam_common.h adam_lr_at)."""
+    out = torch.empty(int(n), dtype=torch.float32, device="cuda")
+    ext().lr_schedule_table(out, float(lr), _sched(sched))
+    return out
+
+
 def adam(p, g, m, v, shadow, step, lr, b1, b2, eps, wd, decoupled, touched=None, now=None, skip_off=0, skip_rows=0,
-         row_len=4, runs=None, run_decay=None):
+         row_len=4, runs=None, run_decay=None, sched=None):
     """Flat-arena Adam.  touched/now (uint8 row flags over [skip_off, skip_off+skip_rows*row_len)) let
     the kernel skip rows with zero state and zero gradient (exact for weight_decay == 0; with
     decoupled decay the caller owes those rows ``adam_lazy_decay``).
     runs = (device int64 [n, 3] table, total float4s, largest end float4) from ``adam_runs``:
     update only those element runs, in one launch.  run_decay = (device fp32 [n], the same values
-    as a list) from ``adam_run_decay``: a weight decay per run (parameter groups) instead of wd."""
+    as a list) from ``adam_run_decay``: a weight decay per run (parameter groups) instead of wd.
+    sched = (kind, warmup, total, offset): ``lr`` is the base rate of that schedule, evaluated on
+    the device from ``step`` (None: constant)."""
     table, total4, end4 = runs if runs is not None else (None, 0, 0)
     rwd, rwd_host = run_decay if run_decay is not None else (None, [])
     ext().adam(p, g, m, v, shadow, step, lr, b1, b2, eps, wd, decoupled, touched, now, skip_off, skip_rows, row_len,
-               table, total4, end4, rwd, rwd_host)
+               table, total4, end4, rwd, rwd_host, _sched(sched))
 
 
-def adam_rows(p, g, m, v, shadow, step, lr, b1, b2, eps, ever, now, row_len, wd=0.0, decoupled=False):
+def adam_rows(p, g, m, v, shadow, step, lr, b1, b2, eps, ever, now, row_len, wd=0.0, decoupled=False, sched=None):
     """Adam over the rows of one [rows][row_len] table (views of the arenas) whose ``ever`` flag
     is set -- the sparse word-embedding update, one wave per 64 row flags.  wd != 0 needs
     decoupled decay; the rows without state then decay through ``adam_lazy_decay``."""
-    ext().adam_rows(p, g, m, v, shadow, step, lr, b1, b2, eps, ever, now, row_len, wd, decoupled)
+    ext().adam_rows(p, g, m, v, shadow, step, lr, b1, b2, eps, ever, now, row_len, wd, decoupled, _sched(sched))
 
 
-def adam_lazy_decay(p, shadow, done, ever, step, adj, lr, wd, row_len, ids=None):
+def adam_lazy_decay(p, shadow, done, ever, step, adj, lr, wd, row_len, ids=None, sched=None):
     """The decoupled decay owed to rows of one [rows][row_len] table that have no Adam state:
     rows ``ids`` (none: every row) are multiplied by 1 - lr * wd once per step not yet applied,
-    up to step - adj completed steps; ``done`` (int32 per row) keeps the count."""
-    ext().adam_lazy_decay(p, shadow, done, ever, step, adj, lr, wd, row_len, ids)
+    up to step - adj completed steps; ``done`` (int32 per row) keeps the count.  With ``sched``
+    each of those multiplications takes the learning rate of its own step."""
+    ext().adam_lazy_decay(p, shadow, done, ever, step, adj, lr, wd, row_len, ids, _sched(sched))
 
 
 def adam_run_decay(decays, device):
