@@ -43,7 +43,7 @@ int fd_gemm_dw2(const void* A0, const void* B0, float* C0, int M0, int N0, const
                 const FdAdamEpi* adams, int defer, int* splits_out, hipStream_t st);
 int fd_gemm_dw2_splits(int M0, int N0, int M1, int N1, int K);
 int fd_gemm_dw_batch(int n, const FdDwProb* probs, int K, const int* step, const float* hyper, int cfg,
-                     const FdAdamRest* rest, const FdLrSched* sched, hipStream_t st);
+                     const FdAdamRest* rest, const FdLrSched* sched, float prox_mu, hipStream_t st);
 int fd_gemm_ln_set_diag(int diag);
 int fd_gemm_dwb_set_mix(int mode);
 long long fd_gemm_dwb_mixed_launches();
@@ -135,10 +135,12 @@ int fd_eval_metrics(const float* logits, const long long* labels, int B, double*
 int fd_adam(float* p, const float* g, float* m, float* v, void* shadow, long long n, const int* step, float lr,
             float b1, float b2, float eps, float wd, int decoupled, const unsigned char* touched,
             const unsigned char* now, long long skip_off, long long skip_rows, int row_len, const long long* runs,
-            int nruns, long long run_total4, const float* run_wd, const FdLrSched* sched, hipStream_t st);
+            int nruns, long long run_total4, const float* run_wd, const FdLrSched* sched, float prox_mu,
+            const float* anchor, hipStream_t st);
 int fd_adam_rows(float* p, const float* g, float* m, float* v, void* shadow, int rows, int row_len, const int* step,
                  float lr, float b1, float b2, float eps, const unsigned char* ever, const unsigned char* now,
-                 float wd, int decoupled, const FdLrSched* sched, hipStream_t st);
+                 float wd, int decoupled, const FdLrSched* sched, float prox_mu, const float* anchor,
+                 hipStream_t st);
 int fd_adam_lazy_decay(float* p, void* shadow, int* done, const unsigned char* ever, int rows, int row_len,
                        const int* step, int adj, float lr, float wd, const void* ids, int ids64, long long n,
                        const FdLrSched* sched, hipStream_t st);
@@ -378,6 +380,26 @@ FdLrSched need_sched(const std::vector<int64_t>& sched, double lr, const char* w
   return s;
 }
 
+// A FedProx proximal coefficient (adam_common.h adam_elem): finite and non-negative.
+void need_mu(double mu, const char* what) {
+  TORCH_CHECK(std::isfinite(mu) && mu >= 0.0, what, ": prox_mu must be finite and >= 0, got ", mu);
+}
+
+// The anchor that goes with state `p` (laid out like it: fp32, contiguous, the same device and
+// element count), or nullptr when none is given -- which only mu == 0 allows.
+const float* need_anchor(double mu, const c10::optional<at::Tensor>& anchor, const at::Tensor& p, const char* what) {
+  need_mu(mu, what);
+  if (!(anchor.has_value() && anchor->defined())) {
+    TORCH_CHECK(mu == 0.0, what, ": prox_mu != 0 needs an anchor");
+    return nullptr;
+  }
+  need(*anchor, at::kFloat, "anchor");
+  TORCH_CHECK(anchor->device() == p.device(), what, ": the anchor must be on the parameters' device");
+  TORCH_CHECK(anchor->numel() == p.numel(), what, ": the anchor has ", anchor->numel(), " elements, the parameters ",
+              p.numel());
+  return anchor->data_ptr<float>();
+}
+
 // Every weight gradient of a backward in one launch (gemm.hip gemm_dw_batch_kernel):
 // Cs[i] (+)= As[i]^T Bs[i] (fp32), As[i] [K_i][M_i], Bs[i] [K_i][N_i] bf16 (K_i % 64 == 0).
 // adam: empty, or [p, m, v, shadow] per problem + the device step counter last (fused
@@ -390,7 +412,11 @@ void gemm_dw_batch(const std::vector<at::Tensor>& As, const std::vector<at::Tens
                    const std::vector<double>& bias_decay = {},
                    const c10::optional<at::Tensor>& rest_wd = c10::nullopt,
                    const std::vector<double>& rest_wd_host = {}, double word_wd = 0.0,
-                   const std::vector<int64_t>& sched = {}) {
+                   const std::vector<int64_t>& sched = {}, double prox_mu = 0.0,
+                   const std::vector<at::Tensor>& anchor = {}) {
+  // prox_mu / anchor (with adam): the FedProx term of the fused step (adam_elem).  anchor: empty, or
+  // per problem the anchor of its matrix (laid out like the gradient) and, with `rest`, one more
+  // entry: the anchor of the whole arena (laid out like the master arena)
   // sched (with adam): the learning-rate schedule whose base rate hp[0] is (need_sched)
   // decay / bias_decay (with adam): per problem the weight decay of its matrix / of its bias
   // (parameter groups; empty = hp's for all).  rest_wd: per-run weight decay of the rest's run
@@ -436,6 +462,11 @@ void gemm_dw_batch(const std::vector<at::Tensor>& As, const std::vector<at::Tens
     pr[i].bias = biases[i].data_ptr<float>();
   }
   TORCH_CHECK(!adam.empty() || sched.empty(), "gemm_dw_batch: sched needs the fused Adam");
+  need_mu(prox_mu, "gemm_dw_batch");
+  TORCH_CHECK(!adam.empty() || (prox_mu == 0.0 && anchor.empty()), "gemm_dw_batch: a proximal term needs the fused Adam");
+  TORCH_CHECK(prox_mu == 0.0 || !anchor.empty(), "gemm_dw_batch: prox_mu != 0 needs the anchors");
+  TORCH_CHECK(anchor.empty() || anchor.size() == n + (rest.empty() ? 0 : 1),
+              "gemm_dw_batch: one anchor per problem, and the arena's with the rest of the step; got ", anchor.size());
   const FdLrSched sc = need_sched(sched, adam.empty() || hp.empty() ? 0.0 : hp[0], "gemm_dw_batch");
   std::vector<FdAdamEpi> ad(n);
   const int* step = nullptr;
@@ -452,6 +483,8 @@ void gemm_dw_batch(const std::vector<at::Tensor>& As, const std::vector<at::Tens
       pr[i].wd = decay.empty() ? ad[0].wd : (float)decay[i];
       pr[i].bias_wd = bias_decay.empty() ? ad[0].wd : (float)bias_decay[i];
     }
+    for (size_t i = 0; i < n && !anchor.empty(); ++i)
+      pr[i].anchor = need_anchor(prox_mu, anchor[i], adam[4 * i], "gemm_dw_batch");
     step = ad[0].step;
     hyper[0] = ad[0].lr; hyper[1] = ad[0].b1; hyper[2] = ad[0].b2; hyper[3] = ad[0].eps; hyper[4] = ad[0].wd;
     hyper[5] = (float)ad[0].decoupled;
@@ -489,6 +522,10 @@ void gemm_dw_batch(const std::vector<at::Tensor>& As, const std::vector<at::Tens
     TORCH_CHECK(word_wd == 0.0 || (rest.size() == 8 && hp[5] != 0.0),
                 "gemm_dw_batch: a decaying sparse word table needs its row flags and decoupled decay");
     rs.wwd = (float)word_wd;
+    if (!anchor.empty()) rs.anchor = need_anchor(prox_mu, anchor[n], rest[0], "gemm_dw_batch rest");
+    TORCH_CHECK(prox_mu == 0.0 || word_wd == 0.0,
+                "gemm_dw_batch: a decaying sparse word table takes no proximal term (its rows without state drift "
+                "from their anchors: use the dense word path)");
     if (rest.size() == 8) {
       need(rest[6], at::kByte, "rest ever");
       need(rest[7], at::kByte, "rest now");
@@ -506,7 +543,7 @@ void gemm_dw_batch(const std::vector<at::Tensor>& As, const std::vector<at::Tens
       }
   }
   check_rc(fd_gemm_dw_batch((int)n, pr.data(), (int)K, step, adam.empty() ? nullptr : hyper, (int)cfg,
-                            rest.empty() ? nullptr : &rs, &sc, stream()),
+                            rest.empty() ? nullptr : &rs, &sc, (float)prox_mu, stream()),
            "gemm_dw_batch");
 }
 
@@ -1577,9 +1614,14 @@ void adam(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, const a
           double wd, bool decoupled, const c10::optional<at::Tensor>& touched, const c10::optional<at::Tensor>& now,
           int64_t skip_off, int64_t skip_rows, int64_t row_len, const c10::optional<at::Tensor>& runs,
           int64_t run_total4, int64_t run_end4, const c10::optional<at::Tensor>& run_wd = c10::nullopt,
-          const std::vector<double>& run_wd_host = {}, const std::vector<int64_t>& sched = {}) {
+          const std::vector<double>& run_wd_host = {}, const std::vector<int64_t>& sched = {},
+          double prox_mu = 0.0, const c10::optional<at::Tensor>& anchor = c10::nullopt) {
   // sched: the learning-rate schedule whose base rate lr is (need_sched; empty = constant)
   const FdLrSched sc = need_sched(sched, lr, "adam");
+  // prox_mu / anchor: the FedProx term (adam_elem); the anchor is laid out like p
+  const float* anc = need_anchor(prox_mu, anchor, p, "adam");
+  TORCH_CHECK(prox_mu == 0.0 || wd == 0.0 || !(touched.has_value() && touched->defined()),
+              "adam: row flags with weight decay take no proximal term");
   // run_wd: per-run weight decay (device fp32 [nruns], parameter groups) with the same values in
   // run_wd_host, checked here; none = wd for every run
   TORCH_CHECK(std::isfinite(wd) && wd >= 0.0, "adam: weight decay must be finite and >= 0");
@@ -1628,7 +1670,7 @@ void adam(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, const a
   check_rc(fd_adam(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
                    ptr<void>(shadow), n, step.data_ptr<int>(), (float)lr, (float)b1, (float)b2, (float)eps, (float)wd,
                    decoupled ? 1 : 0, ptr<const unsigned char>(touched), ptr<const unsigned char>(now), skip_off,
-                   skip_rows, (int)row_len, rp, nruns, total4, rwd, &sc, stream()),
+                   skip_rows, (int)row_len, rp, nruns, total4, rwd, &sc, (float)prox_mu, anc, stream()),
            "adam");
 }
 
@@ -1638,8 +1680,12 @@ void adam(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, const a
 void adam_rows(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, const at::Tensor& v,
                const c10::optional<at::Tensor>& shadow, const at::Tensor& step, double lr, double b1, double b2,
                double eps, const at::Tensor& ever, const c10::optional<at::Tensor>& now, int64_t row_len,
-               double wd = 0.0, bool decoupled = false, const std::vector<int64_t>& sched = {}) {
+               double wd = 0.0, bool decoupled = false, const std::vector<int64_t>& sched = {},
+               double prox_mu = 0.0, const c10::optional<at::Tensor>& anchor = c10::nullopt) {
   const FdLrSched sc = need_sched(sched, lr, "adam_rows");
+  // prox_mu / anchor: the FedProx term (adam_elem); the anchor is the table's, laid out like p
+  const float* anc = need_anchor(prox_mu, anchor, p, "adam_rows");
+  TORCH_CHECK(prox_mu == 0.0 || wd == 0.0, "adam_rows: a decaying table takes no proximal term");
   TORCH_CHECK(std::isfinite(wd) && wd >= 0.0, "adam_rows: weight decay must be finite and >= 0");
   TORCH_CHECK(wd == 0.0 || decoupled, "adam_rows: weight decay needs decoupled decay");
   need(p, at::kFloat, "p");
@@ -1660,7 +1706,7 @@ void adam_rows(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, co
   check_rc(fd_adam_rows(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
                         ptr<void>(shadow), (int)rows, (int)row_len, step.data_ptr<int>(), (float)lr, (float)b1,
                         (float)b2, (float)eps, ever.data_ptr<unsigned char>(), ptr<const unsigned char>(now),
-                        (float)wd, decoupled ? 1 : 0, &sc, stream()),
+                        (float)wd, decoupled ? 1 : 0, &sc, (float)prox_mu, anc, stream()),
            "adam_rows");
 }
 
@@ -1766,7 +1812,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adam_rows", &adam_rows, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("shadow"),
         py::arg("step"), py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("ever"), py::arg("now"),
         py::arg("row_len"), py::arg("wd") = 0.0, py::arg("decoupled") = false,
-        py::arg("sched") = std::vector<int64_t>{});
+        py::arg("sched") = std::vector<int64_t>{}, py::arg("prox_mu") = 0.0, py::arg("anchor") = py::none());
   m.def("adam_lazy_decay", &adam_lazy_decay, py::arg("p"), py::arg("shadow"), py::arg("done"), py::arg("ever"),
         py::arg("step"), py::arg("adj"), py::arg("lr"), py::arg("wd"), py::arg("row_len"),
         py::arg("ids") = py::none(), py::arg("sched") = std::vector<int64_t>{});
@@ -1782,7 +1828,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("rest_i") = std::vector<int64_t>{}, py::arg("decay") = std::vector<double>{},
         py::arg("bias_decay") = std::vector<double>{}, py::arg("rest_wd") = py::none(),
         py::arg("rest_wd_host") = std::vector<double>{}, py::arg("word_wd") = 0.0,
-        py::arg("sched") = std::vector<int64_t>{});
+        py::arg("sched") = std::vector<int64_t>{}, py::arg("prox_mu") = 0.0,
+        py::arg("anchor") = std::vector<at::Tensor>{});
   m.def("gemm_colsum", &gemm_colsum, py::arg("epi"), py::arg("A"), py::arg("B"), py::arg("C"), py::arg("aux"),
         py::arg("res"), py::arg("colsum"), py::arg("aux_out") = py::none(), py::arg("kind") = 0,
         py::arg("prefetch") = py::none());

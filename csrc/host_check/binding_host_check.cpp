@@ -44,6 +44,10 @@ void sched(const FdLrSched* s, const char* what) {
       s->total >= lim || s->offset >= lim || (s->kind == 1 && s->warmup > s->total))
     violations.push_back(std::string(what) + ": learning-rate schedule out of range");
 }
+// a FedProx coefficient as the kernels take it (adam_common.h adam_elem)
+void mu(float m, const char* what) {
+  if (!(m >= 0.f) || !std::isfinite(m)) violations.push_back(std::string(what) + ": negative / non-finite prox_mu");
+}
 }  // namespace hc
 
 // ------------------------------------------------------------------ stub launchers
@@ -121,9 +125,11 @@ int fd_gemm_dw2(const void* A0, const void* B0, float* C0, int M0, int N0, const
 }
 int fd_gemm_dw2_splits(int, int, int, int, int) { return 1; }
 int fd_gemm_dw_batch(int n, const FdDwProb* probs, int K, const int* step, const float* hyper, int cfg,
-                     const FdAdamRest* rest, const FdLrSched* sched, hipStream_t) {
+                     const FdAdamRest* rest, const FdLrSched* sched, float prox_mu, hipStream_t) {
   ++hc::calls;
   hc::sched(sched, "dw_batch");
+  hc::mu(prox_mu, "dw_batch");
+  if (prox_mu != 0.f && !hyper) hc::violations.push_back("dw_batch: a proximal term without the fused Adam");
   if (sched && sched->kind != 0 && !hyper) hc::violations.push_back("dw_batch: a schedule without the fused Adam");
   if (rest) {
     if (!hyper || !step) hc::violations.push_back("dw_batch rest without the fused Adam");
@@ -135,6 +141,14 @@ int fd_gemm_dw_batch(int n, const FdDwProb* probs, int K, const int* step, const
       hc::span(rest->ever, rest->wrows, "dw_batch rest ever");
       hc::span(rest->now, rest->wrows, "dw_batch rest now");
       hc::span(rest->p + rest->woff, (long long)rest->wrows * rest->wrow4 * 16, "dw_batch rest word rows");
+    }
+    if (prox_mu != 0.f) {  // the anchor arena: the word rows and every run, at the offsets of p
+      if (rest->ever && rest->wwd != 0.f) hc::violations.push_back("dw_batch: a proximal term on a decaying sparse word table");
+      if (!rest->anchor) hc::violations.push_back("dw_batch: a proximal term without the rest's anchor");
+      else if (rest->ever)
+        hc::span(rest->anchor + rest->woff, (long long)rest->wrows * rest->wrow4 * 16, "dw_batch rest word anchor");
+      for (int i = 0; rest->anchor && rest->runs && i < rest->nruns; ++i)
+        hc::span(rest->anchor + 4 * rest->runs[3 * i], rest->runs[3 * i + 1] * 16, "dw_batch rest run anchor");
     }
   }
   if (n <= 0 || n > 32) hc::violations.push_back("dw_batch: problem count");
@@ -151,6 +165,9 @@ int fd_gemm_dw_batch(int n, const FdDwProb* probs, int K, const int* step, const
       hc::span(q.m, mn * 4, "dw_batch adam m");
       hc::span(q.v, mn * 4, "dw_batch adam v");
       hc::opt_span(q.sh, mn * 2, "dw_batch adam shadow");
+      if (prox_mu != 0.f) hc::span(q.anchor, mn * 4, "dw_batch adam anchor");
+      if (prox_mu != 0.f && q.bias && rest && rest->anchor && rest->g)
+        hc::span(rest->anchor + (q.bias - rest->g), (long long)q.M * 4, "dw_batch bias anchor");
       hc::span(step, 4, "dw_batch step");
       if (!hyper) hc::violations.push_back("dw_batch: fused Adam without hyper-parameters");
       if (!(q.wd >= 0.f) || !(q.bias_wd >= 0.f)) hc::violations.push_back("dw_batch: negative / NaN weight decay");
@@ -163,9 +180,12 @@ int fd_gemm_dw_batch(int n, const FdDwProb* probs, int K, const int* step, const
 }
 int fd_adam_rows(float* p, const float* g, float* m, float* v, void* shadow, int rows, int row_len, const int* step,
                  float, float, float, float, const unsigned char* ever, const unsigned char* now, float wd,
-                 int decoupled, const FdLrSched* sched, hipStream_t) {
+                 int decoupled, const FdLrSched* sched, float prox_mu, const float* anchor, hipStream_t) {
   ++hc::calls;
   hc::sched(sched, "adam_rows");
+  hc::mu(prox_mu, "adam_rows");
+  if (prox_mu != 0.f) hc::span(anchor, (long long)rows * row_len * 4, "adam_rows anchor");
+  if (prox_mu != 0.f && wd != 0.f) hc::violations.push_back("adam_rows: a proximal term on a decaying table");
   if (wd != 0.f && !decoupled) hc::violations.push_back("adam_rows: coupled weight decay on flagged rows");
   const long long n = (long long)rows * row_len;
   hc::span(p, n * 4, "adam_rows p");
@@ -598,9 +618,11 @@ int fd_eval_metrics(const float*, const long long*, int, double*, long long*, fl
 int fd_adam(float* p, const float* g, float* m, float* v, void* shadow, long long n, const int* step, float, float,
             float, float, float, int, const unsigned char* touched, const unsigned char* now, long long skip_off,
             long long skip_rows, int row_len, const long long* runs, int nruns, long long run_total4,
-            const float* run_wd, const FdLrSched* sched, hipStream_t) {
+            const float* run_wd, const FdLrSched* sched, float prox_mu, const float* anchor, hipStream_t) {
   ++hc::calls;
   hc::sched(sched, "adam");
+  hc::mu(prox_mu, "adam");
+  if (prox_mu != 0.f) hc::span(anchor, n * 4, "adam anchor");
   if (run_wd) {
     if (!runs) hc::violations.push_back("adam: run decays without a run table");
     hc::span(run_wd, (long long)nruns * 4, "adam run decays");
@@ -789,6 +811,36 @@ int main() {
         gemm_dw_batch(As, Bs, Cs, acc, st, hpw, -1, {}, rest, ri, {}, {}, none, {}, -0.01); });
       expect_reject("dw_batch rest decays without rest", [&] {
         gemm_dw_batch(As, Bs, Cs, acc, st, hpw, -1, {}, {}, {}, {}, {}, rw, {0.01, 0.0}, 0.0); });
+      // FedProx: an anchor per fused matrix, and the arena's with the rest of the step
+      std::vector<at::Tensor> anc, anc_short;
+      for (auto& sh : shapes) anc.push_back(T_({sh[0] * sh[1]}, f32));
+      anc_short = anc;
+      anc_short[2] = T_({3072 * 768 - 4}, f32);
+      auto anc_rest = anc, anc_rest_short = anc;
+      anc_rest.push_back(T_({an}, f32));
+      anc_rest_short.push_back(T_({an - 4}, f32));
+      expect_ok("dw_batch prox", [&] {
+        gemm_dw_batch(As, Bs, Cs, acc, st, hpw, -1, {}, {}, {}, {}, {}, none, {}, 0.0, {}, 0.1, anc); });
+      expect_ok("dw_batch prox rest", [&] {
+        gemm_dw_batch(As, Bs, Cs, acc, st, hpw, -1, {}, rest, ri, {}, {}, none, {}, 0.0, {}, 0.1, anc_rest); });
+      expect_ok("dw_batch prox mu 0", [&] {
+        gemm_dw_batch(As, Bs, Cs, acc, st, hpw, -1, {}, rest, ri, {}, {}, none, {}, 0.0, {}, 0.0, anc_rest); });
+      expect_reject("dw_batch prox no anchor", [&] {
+        gemm_dw_batch(As, Bs, Cs, acc, st, hpw, -1, {}, {}, {}, {}, {}, none, {}, 0.0, {}, 0.1, {}); });
+      expect_reject("dw_batch prox short anchor", [&] {
+        gemm_dw_batch(As, Bs, Cs, acc, st, hpw, -1, {}, {}, {}, {}, {}, none, {}, 0.0, {}, 0.1, anc_short); });
+      expect_reject("dw_batch prox rest without the arena's anchor", [&] {
+        gemm_dw_batch(As, Bs, Cs, acc, st, hpw, -1, {}, rest, ri, {}, {}, none, {}, 0.0, {}, 0.1, anc); });
+      expect_reject("dw_batch prox rest short anchor", [&] {
+        gemm_dw_batch(As, Bs, Cs, acc, st, hpw, -1, {}, rest, ri, {}, {}, none, {}, 0.0, {}, 0.1, anc_rest_short); });
+      expect_reject("dw_batch prox + decaying sparse word table", [&] {
+        gemm_dw_batch(As, Bs, Cs, acc, st, hpw, -1, {}, rest, ri, {}, {}, none, {}, 0.01, {}, 0.1, anc_rest); });
+      expect_reject("dw_batch prox without adam", [&] {
+        gemm_dw_batch(As, Bs, Cs, acc, {}, {}, -1, {}, {}, {}, {}, {}, none, {}, 0.0, {}, 0.1, anc); });
+      expect_reject("dw_batch prox mu negative", [&] {
+        gemm_dw_batch(As, Bs, Cs, acc, st, hpw, -1, {}, {}, {}, {}, {}, none, {}, 0.0, {}, -0.1, anc); });
+      expect_reject("dw_batch prox mu inf", [&] {
+        gemm_dw_batch(As, Bs, Cs, acc, st, hpw, -1, {}, {}, {}, {}, {}, none, {}, 0.0, {}, INFINITY, anc); });
     }
     auto Bbad = Bs;
     Bbad[2] = T_({2000, 768}, bf);
@@ -1058,6 +1110,39 @@ int main() {
                                             4, runs, 320, 768, none, {}, lin); });
     expect_reject("adam rows lr NaN", [&] { adam_rows(p, g, m, v, sh, step, std::nan(""), 0.9, 0.999, 1e-8, ever, now,
                                                       64); });
+    // FedProx: the anchor is laid out like p
+    {
+      const c10::optional<at::Tensor> anc = T_({n}, f32), anc_short = T_({n - 4}, f32), anc_bf = T_({n}, bf);
+      expect_ok("adam prox", [&] { adam(p, g, m, v, sh, step, 2e-5, 0.9, 0.999, 1e-8, 0.01, true, none, none, 0, 0, 4,
+                                        runs, 320, 768, none, {}, {}, 0.1, anc); });
+      expect_ok("adam prox mu 0, no anchor", [&] { adam(p, g, m, v, sh, step, 2e-5, 0.9, 0.999, 1e-8, 0, false, none,
+                                                        none, 0, 0, 4, runs, 320, 768, none, {}, {}, 0.0, none); });
+      expect_ok("adam prox flags", [&] { adam(p, g, m, v, sh, step, 2e-5, 0.9, 0.999, 1e-8, 0, false, ever, now, 0, 64,
+                                              64, none, 0, 0, none, {}, {}, 0.1, anc); });
+      expect_reject("adam prox no anchor", [&] { adam(p, g, m, v, sh, step, 2e-5, 0.9, 0.999, 1e-8, 0, false, none, none,
+                                                      0, 0, 4, runs, 320, 768, none, {}, {}, 0.1, none); });
+      expect_reject("adam prox short anchor", [&] { adam(p, g, m, v, sh, step, 2e-5, 0.9, 0.999, 1e-8, 0, false, none,
+                                                         none, 0, 0, 4, runs, 320, 768, none, {}, {}, 0.1, anc_short); });
+      expect_reject("adam prox short anchor, mu 0", [&] { adam(p, g, m, v, sh, step, 2e-5, 0.9, 0.999, 1e-8, 0, false,
+                                                               none, none, 0, 0, 4, runs, 320, 768, none, {}, {}, 0.0,
+                                                               anc_short); });
+      expect_reject("adam prox anchor dtype", [&] { adam(p, g, m, v, sh, step, 2e-5, 0.9, 0.999, 1e-8, 0, false, none,
+                                                         none, 0, 0, 4, runs, 320, 768, none, {}, {}, 0.1, anc_bf); });
+      expect_reject("adam prox mu negative", [&] { adam(p, g, m, v, sh, step, 2e-5, 0.9, 0.999, 1e-8, 0, false, none,
+                                                        none, 0, 0, 4, runs, 320, 768, none, {}, {}, -0.1, anc); });
+      expect_reject("adam prox mu NaN", [&] { adam(p, g, m, v, sh, step, 2e-5, 0.9, 0.999, 1e-8, 0, false, none, none, 0,
+                                                   0, 4, runs, 320, 768, none, {}, {}, std::nan(""), anc); });
+      expect_reject("adam prox flags + decay", [&] { adam(p, g, m, v, sh, step, 2e-5, 0.9, 0.999, 1e-8, 0.01, true, ever,
+                                                          now, 0, 64, 64, none, 0, 0, none, {}, {}, 0.1, anc); });
+      expect_ok("adam rows prox", [&] { adam_rows(p, g, m, v, sh, step, 2e-5, 0.9, 0.999, 1e-8, ever, now, 64, 0.0, false,
+                                                  {}, 0.1, anc); });
+      expect_reject("adam rows prox no anchor", [&] { adam_rows(p, g, m, v, sh, step, 2e-5, 0.9, 0.999, 1e-8, ever, now,
+                                                                64, 0.0, false, {}, 0.1, none); });
+      expect_reject("adam rows prox short anchor", [&] { adam_rows(p, g, m, v, sh, step, 2e-5, 0.9, 0.999, 1e-8, ever,
+                                                                   now, 64, 0.0, false, {}, 0.1, anc_short); });
+      expect_reject("adam rows prox + decay", [&] { adam_rows(p, g, m, v, sh, step, 2e-5, 0.9, 0.999, 1e-8, ever, now, 64,
+                                                              0.01, true, {}, 0.1, anc); });
+    }
     expect_reject("lr table lr NaN", [&] { lr_schedule_table(T_({4}, f32), std::nan(""), lin); });
     expect_reject("lr table empty", [&] { lr_schedule_table(T_({0}, f32), 2e-5, lin); });
     expect_reject("lr table no schedule", [&] { lr_schedule_table(T_({4}, f32), 2e-5, {}); });

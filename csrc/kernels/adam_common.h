@@ -6,11 +6,15 @@
 #pragma once
 
 // The Adam update of one element (torch.optim.Adam / AdamW defaults: bias-corrected, eps outside
-// the square root; step_size = lr / bc1, inv_sqrt_bc2 = 1 / sqrt(bc2)).
-DEV void adam_elem(float lr, float b1, float b2, float eps, float wd, int decoupled, float& p, float g, float& m,
-                   float& v, float step_size, float inv_sqrt_bc2) {
+// the square root; step_size = lr / bc1, inv_sqrt_bc2 = 1 / sqrt(bc2)).  mu != 0: the FedProx proximal
+// term -- the gradient gets mu * (p - a), a the element's anchor (its value when the round began),
+// taken from p as loaded, before a decoupled decay multiplies it: p.grad += mu * (p - p_global), then
+// torch.optim.Adam / AdamW.  With mu == 0 the anchor is never looked at (callers pass 0).
+DEV void adam_elem(float lr, float b1, float b2, float eps, float wd, int decoupled, float mu, float a, float& p,
+                   float g, float& m, float& v, float step_size, float inv_sqrt_bc2) {
 #pragma clang fp contract(off)
   float gr = g;
+  if (mu != 0.f) gr += mu * (p - a);
   if (wd != 0.f) {
     if (decoupled) p *= 1.f - lr * wd;
     else gr += wd * p;
@@ -83,6 +87,10 @@ struct AdamArgs {
   // Per-run weight decay, parallel to the run table (nullable = wd for every run): parameter
   // groups -- biases and LayerNorm affines usually decay by 0 (engine/optim.py no_decay).
   const float* run_wd;
+  // FedProx: mu != 0 adds mu * (p - anchor) to every gradient (adam_elem); anchor is laid out like p
+  // and only read when mu != 0 (nullable otherwise)
+  const float* anchor;
+  float mu;
   // lr is the base rate of this schedule; a kernel replaces lr by the step's rate (adam_bias_corr)
   // before the element loops
   FdLrSched sched;
@@ -112,16 +120,24 @@ DEV void st_nt(float4* p, float4 v) {
   __builtin_nontemporal_store(f32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4*>(p));
 }
 
-// The Adam update of 4 elements (adam_elem each) with weight decay wd.
+// float4 i of the anchor, read once per step (nontemporal) -- and only under a proximal term: the
+// branch is uniform over the launch, so mu == 0 adds no traffic.
+DEV float4 ld_anchor(const AdamArgs& a, long long i) {
+  return a.mu != 0.f ? ld_nt(reinterpret_cast<const float4*>(a.anchor) + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// The Adam update of 4 elements (adam_elem each) with weight decay wd and anchor a4.
 DEV void adam_math4(const AdamArgs& a, float wd, float (&pp)[4], const float (&gg)[4], float (&mm)[4],
-                    float (&vv)[4], float step_size, float inv_sqrt_bc2) {
+                    float (&vv)[4], float4 a4, float step_size, float inv_sqrt_bc2) {
+  const float aa[4] = {a4.x, a4.y, a4.z, a4.w};
 #pragma unroll
   for (int e = 0; e < 4; ++e)
-    adam_elem(a.lr, a.b1, a.b2, a.eps, wd, a.decoupled, pp[e], gg[e], mm[e], vv[e], step_size, inv_sqrt_bc2);
+    adam_elem(a.lr, a.b1, a.b2, a.eps, wd, a.decoupled, a.mu, aa[e], pp[e], gg[e], mm[e], vv[e], step_size,
+              inv_sqrt_bc2);
 }
 DEV void adam_math4(const AdamArgs& a, float (&pp)[4], const float (&gg)[4], float (&mm)[4], float (&vv)[4],
-                    float step_size, float inv_sqrt_bc2) {
-  adam_math4(a, a.wd, pp, gg, mm, vv, step_size, inv_sqrt_bc2);
+                    float4 a4, float step_size, float inv_sqrt_bc2) {
+  adam_math4(a, a.wd, pp, gg, mm, vv, a4, step_size, inv_sqrt_bc2);
 }
 
 // One flagged row of a [rows][row4] float4 table starting at float4 base4 (one wave; gradient 0
@@ -135,9 +151,10 @@ DEV void adam_row(const AdamArgs& a, long long base4, int row, int row4, int lan
     const float4 g = gvalid ? ld_nt(reinterpret_cast<const float4*>(a.g) + i) : make_float4(0.f, 0.f, 0.f, 0.f);
     const float4 m = ld_nt(reinterpret_cast<const float4*>(a.m) + i);
     const float4 v = ld_nt(reinterpret_cast<const float4*>(a.v) + i);
+    const float4 a4 = ld_anchor(a, i);
     float pp[4] = {p.x, p.y, p.z, p.w}, gg[4] = {g.x, g.y, g.z, g.w};
     float mm[4] = {m.x, m.y, m.z, m.w}, vv[4] = {v.x, v.y, v.z, v.w};
-    adam_math4(a, pp, gg, mm, vv, step_size, inv_sqrt_bc2);
+    adam_math4(a, pp, gg, mm, vv, a4, step_size, inv_sqrt_bc2);
     st_nt(reinterpret_cast<float4*>(a.p) + i, make_float4(pp[0], pp[1], pp[2], pp[3]));
     st_nt(reinterpret_cast<float4*>(a.m) + i, make_float4(mm[0], mm[1], mm[2], mm[3]));
     st_nt(reinterpret_cast<float4*>(a.v) + i, make_float4(vv[0], vv[1], vv[2], vv[3]));
@@ -171,9 +188,10 @@ DEV void adam_flat4(const AdamArgs& a, long long vi, float step_size, float inv_
     m = reinterpret_cast<float4*>(a.m)[i];
     v = reinterpret_cast<float4*>(a.v)[i];
   }
+  const float4 a4 = ld_anchor(a, i);
   float pp[4] = {p.x, p.y, p.z, p.w}, gg[4] = {g.x, g.y, g.z, g.w};
   float mm[4] = {m.x, m.y, m.z, m.w}, vv[4] = {v.x, v.y, v.z, v.w};
-  adam_math4(a, wd, pp, gg, mm, vv, step_size, inv_sqrt_bc2);
+  adam_math4(a, wd, pp, gg, mm, vv, a4, step_size, inv_sqrt_bc2);
   if constexpr (NTP)
     st_nt(reinterpret_cast<float4*>(a.p) + i, make_float4(pp[0], pp[1], pp[2], pp[3]));
   else
@@ -195,10 +213,11 @@ DEV void adam_flat4(const AdamArgs& a, long long vi, float step_size, float inv_
 DEV void adam_row768(const AdamArgs& a, int row, int lane, float step_size, float inv_sqrt_bc2) {
   constexpr int C = 3;  // 192 float4 / 64 lanes
   const bool gvalid = a.now == nullptr || a.now[row] != 0;
-  float4 p[C], g[C], m[C], v[C];
+  float4 p[C], g[C], m[C], v[C], an[C];
 #pragma unroll
   for (int k = 0; k < C; ++k) {
     const long long i = (long long)row * 192 + lane + 64 * k;
+    an[k] = ld_anchor(a, i);
     p[k] = ld_nt(reinterpret_cast<const float4*>(a.p) + i);
     g[k] = gvalid ? ld_nt(reinterpret_cast<const float4*>(a.g) + i) : make_float4(0.f, 0.f, 0.f, 0.f);
     m[k] = ld_nt(reinterpret_cast<const float4*>(a.m) + i);
@@ -209,7 +228,7 @@ DEV void adam_row768(const AdamArgs& a, int row, int lane, float step_size, floa
     const long long i = (long long)row * 192 + lane + 64 * k;
     float pp[4] = {p[k].x, p[k].y, p[k].z, p[k].w}, gg[4] = {g[k].x, g[k].y, g[k].z, g[k].w};
     float mm[4] = {m[k].x, m[k].y, m[k].z, m[k].w}, vv[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
-    adam_math4(a, pp, gg, mm, vv, step_size, inv_sqrt_bc2);
+    adam_math4(a, pp, gg, mm, vv, an[k], step_size, inv_sqrt_bc2);
     st_nt(reinterpret_cast<float4*>(a.p) + i, make_float4(pp[0], pp[1], pp[2], pp[3]));
     st_nt(reinterpret_cast<float4*>(a.m) + i, make_float4(mm[0], mm[1], mm[2], mm[3]));
     st_nt(reinterpret_cast<float4*>(a.v) + i, make_float4(vv[0], vv[1], vv[2], vv[3]));

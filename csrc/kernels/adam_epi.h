@@ -22,6 +22,10 @@ struct FdAdamEpi {
   const int* step;    // device step counter (already advanced for this step)
   float lr, b1, b2, eps, wd;   // lr: this step's rate (a schedule is resolved by whoever fills this in)
   int decoupled;      // AdamW-style decay
+  // FedProx (adam_common.h adam_elem): mu != 0 adds mu * (p - anchor) to the gradient; anchor is
+  // laid out like p and read only when mu != 0 (nullable otherwise)
+  const float* anchor;
+  float mu;
 };
 
 // One weight-gradient problem of the all-layer launch (gemm.hip gemm_dw_batch_kernel):
@@ -46,6 +50,7 @@ struct FdDwProb {
   float* bias;
   int half;           // filled by the launcher: 1 = tiled 256 x 128 (the mixed schedule's tail class)
   float bias_wd;      // the bias's weight decay, when the launch's tiles also apply its Adam step
+  const float* anchor;  // FedProx anchor of the matrix, laid out like p (nullable: the launch's mu == 0)
 };
 
 // The rest of the optimizer step, run by extra blocks of the all-layer dW launch beside its last
@@ -75,6 +80,9 @@ struct FdAdamRest {
   int first;                    // the rest blocks lead the grid (else they follow the tiles)
   const float* run_wd;
   float wwd;
+  // FedProx anchor of the whole arena, laid out like p (the word table's and the qkv biases' at
+  // the same offsets); nullable: the launch's mu == 0
+  const float* anchor;
 };
 
 #define FD_LN_XSITES 128

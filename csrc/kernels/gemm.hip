@@ -51,7 +51,13 @@ enum Epi : int {
   EPI_LN_BWD = 7,     // C(bf16) = LN backward of dy = acc + res    (p.ln; gemm_ln_kernel only)
   EPI_LN2 = 8,        // EPI_LN / EPI_LN_BWD of a 128 x 64 tile from the two K halves of a 128 x 128
   EPI_LN2_BWD = 9,    //   product tile (gemm_ln2_kernel only; p.ln2_half = which half this block runs)
+  // EPI_F32 whose fused Adam carries a FedProx term (adam.mu / adam.anchor, acol_a): the all-layer
+  // dW launch's PROX kernels only.  A template arm of its own, so every kernel of the default path
+  // (and the per-layer EPI_F32 kernels, which refuse a proximal term) compiles from the code it had
+  // before the term existed.
+  EPI_F32P = 10,
 };
+constexpr bool epi_f32(int e) { return e == EPI_F32 || e == EPI_F32P; }
 
 struct GemmParams {
   const bf16_t* A;
@@ -93,6 +99,7 @@ struct GemmParams {
   float* acol_v;
   uint16_t* acol_sh;
   float acol_wd;         // the bias's weight decay (its parameter group's, not the matrix's)
+  const float* acol_a;   // the bias's FedProx anchor (read only when adam.mu != 0)
   int ln2_half;          // EPI_LN2*: this block's K half and the 64-column half of the tile it finishes
 };
 
@@ -256,8 +263,8 @@ struct EpiTraits {
   static constexpr bool LN = (EPI == EPI_LN || EPI == EPI_LN_BWD || LN2);
   // fp32 weight-gradient tiles too large to stage in LDS (256 x 192, 256 x 256) are finished
   // straight from the accumulators (direct_f32_epilogue): 16-byte stores per lane
-  static constexpr bool DIRECT = EPI == EPI_F32 && BM * (BN * 4 + 16) > LDS_MAX;
-  static constexpr bool F32S = (EPI == EPI_F32 && !DIRECT) || ((ELEM || LN) && BM * (BN * 4 + 16) <= LDS_MAX);
+  static constexpr bool DIRECT = epi_f32(EPI) && BM * (BN * 4 + 16) > LDS_MAX;
+  static constexpr bool F32S = (epi_f32(EPI) && !DIRECT) || ((ELEM || LN) && BM * (BN * 4 + 16) <= LDS_MAX);
   static constexpr int ES = F32S ? 4 : 2;
   static constexpr int BYTES = DIRECT ? 0 : BM * (BN * ES + 16);
 };
@@ -272,13 +279,21 @@ DEV void st_nt4(float* p, float4 v) {
 
 // Adam on 4 consecutive elements of a finished gradient tile: adam_elem (adam_common.h), as in
 // adam_kernel (head_optim.hip), so a fused step matches the unfused one bitwise.
+// PROX (EPI_F32P): the launch may carry a FedProx term.
+template <bool PROX>
 DEV float4 adam_epi4(const FdAdamEpi& a, size_t i, float4 g4, float step_size, float inv_sqrt_bc2) {
   const float4 p4 = ld_nt4(a.p + i), m4 = ld_nt4(a.m + i), v4 = ld_nt4(a.v + i);
+  // the FedProx anchor: read once per step like m / v, and only under a proximal term (uniform
+  // over the launch: mu == 0 adds no traffic)
+  const float mu = PROX ? a.mu : 0.f;
+  const float4 a4 = mu != 0.f ? ld_nt4(a.anchor + i) : make_float4(0.f, 0.f, 0.f, 0.f);
   float pp[4] = {p4.x, p4.y, p4.z, p4.w}, gg[4] = {g4.x, g4.y, g4.z, g4.w};
   float mm[4] = {m4.x, m4.y, m4.z, m4.w}, vv[4] = {v4.x, v4.y, v4.z, v4.w};
+  const float aa[4] = {a4.x, a4.y, a4.z, a4.w};
 #pragma unroll
   for (int e = 0; e < 4; ++e)
-    adam_elem(a.lr, a.b1, a.b2, a.eps, a.wd, a.decoupled, pp[e], gg[e], mm[e], vv[e], step_size, inv_sqrt_bc2);
+    adam_elem(a.lr, a.b1, a.b2, a.eps, a.wd, a.decoupled, mu, aa[e], pp[e], gg[e], mm[e], vv[e], step_size,
+              inv_sqrt_bc2);
   st_nt4(a.p + i, make_float4(pp[0], pp[1], pp[2], pp[3]));
   st_nt4(a.m + i, make_float4(mm[0], mm[1], mm[2], mm[3]));
   st_nt4(a.v + i, make_float4(vv[0], vv[1], vv[2], vv[3]));
@@ -287,7 +302,7 @@ DEV float4 adam_epi4(const FdAdamEpi& a, size_t i, float4 g4, float step_size, f
 }
 
 // Weight-gradient (fp32) epilogue; see GemmParams::out for the two modes.
-template <int BM, int BN, int NT>
+template <int BM, int BN, int NT, bool PROX = false>
 DEV void f32_epilogue(const GemmParams& p, const char* smem, int ldc_lds, int m0, int n0, int tid) {
   constexpr int CPR = BN / 4;  // 4 fp32 per chunk
   if (p.out == nullptr) {      // legacy: slab z, reduced by a separate launch
@@ -323,7 +338,7 @@ DEV void f32_epilogue(const GemmParams& p, const char* smem, int ldc_lds, int m0
       g.x += o.x; g.y += o.y; g.z += o.z; g.w += o.w;
     }
     if (adam) {
-      adam_epi4(p.adam, i, g, step_size, inv_sqrt_bc2);
+      adam_epi4<PROX>(p.adam, i, g, step_size, inv_sqrt_bc2);
     } else {
       *reinterpret_cast<float4*>(p.out + i) = g;
     }
@@ -428,7 +443,7 @@ DEV void staged_epilogue(const GemmParams& p, const f32x4 (&acc)[TM / 16][TN / 1
   }
   __syncthreads();
   if (p.diag & 4) return;
-  if constexpr (EPI == EPI_F32) {  // (weight gradients: no next-launch prefetch)
+  if constexpr (epi_f32(EPI)) {  // (weight gradients: no next-launch prefetch)
     staged_epilogue_out<BM, BN, TM, TN, EPI, NT>(p, smem, m0, n0, tid, pre);
   } else {
     // the next launch's weight (p.ln.pf, fd_gemm_pf): issued after every load this epilogue waits for
@@ -475,8 +490,8 @@ DEV void staged_epilogue_out(const GemmParams& p, char* smem, int m0, int n0, in
       }
     }
     if constexpr (WT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing thread drains
-  } else if constexpr (EPI == EPI_F32) {
-    f32_epilogue<BM, BN, NT>(p, smem, LDC, m0, n0, tid);
+  } else if constexpr (epi_f32(EPI)) {
+    f32_epilogue<BM, BN, NT, EPI == EPI_F32P>(p, smem, LDC, m0, n0, tid);
   } else {
     // 8 fp32 per chunk: two float4 LDS reads, then one 16-byte load / store per global stream
     constexpr int CPR = BN / 8;
@@ -1143,12 +1158,12 @@ DEV void gemm_tile_at(const GemmParams& p, int tm, int tn, char* smem) {
   bf16x8 a0[MI], b0[NI], a1[MI], b1[NI];
   // column sums of A (EPI_F32 acol): lane l's A fragments hold 8 k values of column m = l % 16
   // of each 16-column block; only the first column block's tiles and their wc == 0 waves sum
-  const bool acs = EPI == EPI_F32 && p.acol != nullptr && tn == 0 && wc == 0;
+  const bool acs = epi_f32(EPI) && p.acol != nullptr && tn == 0 && wc == 0;
   float asum[MI];
 #pragma unroll
   for (int i = 0; i < MI; ++i) asum[i] = 0.f;
   auto sum_a = [&]() {
-    if constexpr (EPI == EPI_F32) {
+    if constexpr (epi_f32(EPI)) {
       if (acs) {
 #pragma unroll
         for (int i = 0; i < MI; ++i) {
@@ -1256,7 +1271,7 @@ DEV void gemm_tile_at(const GemmParams& p, int tm, int tn, char* smem) {
     }
   }
   FD_STAMP(2);
-  if constexpr (EPI == EPI_F32) {
+  if constexpr (epi_f32(EPI)) {
     if (acs) {  // the 4 lane groups of a column hold disjoint k: fold them, lanes 0-15 store
 #pragma unroll
       for (int i = 0; i < MI; ++i) {
@@ -1269,8 +1284,13 @@ DEV void gemm_tile_at(const GemmParams& p, int tm, int tn, char* smem) {
             float ss, inv;
             adam_bias_corr(p.adam.step, p.adam.lr, p.adam.b1, p.adam.b2, ss, inv);
             float pb = p.acol_p[m], mb = p.acol_m[m], vb = p.acol_v[m];
-            adam_elem(p.adam.lr, p.adam.b1, p.adam.b2, p.adam.eps, p.acol_wd, p.adam.decoupled, pb, s, mb, vb, ss,
-                      inv);
+            float mu = 0.f, ab = 0.f;  // the FedProx term and the bias's anchor (EPI_F32P only)
+            if constexpr (EPI == EPI_F32P) {
+              mu = p.adam.mu;
+              if (mu != 0.f) ab = p.acol_a[m];
+            }
+            adam_elem(p.adam.lr, p.adam.b1, p.adam.b2, p.adam.eps, p.acol_wd, p.adam.decoupled, mu, ab, pb, s, mb, vb,
+                      ss, inv);
             p.acol_p[m] = pb;
             p.acol_m[m] = mb;
             p.acol_v[m] = vb;
@@ -1303,7 +1323,7 @@ DEV void gemm_tile_at(const GemmParams& p, int tm, int tn, char* smem) {
         }
       }
       __syncthreads();
-      f32_epilogue<TM, BN, 64 * NW>(p, smem, LDC, m0 + band * TM, n0, tid);
+      f32_epilogue<TM, BN, 64 * NW, EPI == EPI_F32P>(p, smem, LDC, m0 + band * TM, n0, tid);
     }
   } else if constexpr (EpiTraits<EPI, BM, BN>::LN2) {
     static_assert((BM == 128 || BM == 256) && BN == 128 && WM == 4 && TN == 64, "two-K-half LayerNorm tile");
@@ -1785,6 +1805,7 @@ struct DwBatch {
   float lr, b1, b2, eps, wd;
   int decoupled;
   FdLrSched sched;  // lr is its base rate (adam_common.h adam_lr_at)
+  float mu;         // FedProx (adam_elem): != 0 -> every problem with p and the rest carry an anchor
   FdAdamRest rest;  // rest.p != nullptr: blocks [ntiles, ntiles + rest blocks) finish the optimizer step
   // Mixed schedule (fd_gemm_dw_batch plan_dwb_mix; mixed != 0): problems are ordered in three classes
   // -- [long 256 x 256 | long 256 x 128 (half) | short-K 256 x 256] -- and each class is dealt to the
@@ -1801,8 +1822,11 @@ struct DwBatch {
 constexpr int DWB_HBM = 256, DWB_HBN = 128, DWB_HWM = 4, DWB_HWN = 2;
 
 // One tile of the batch: logical tile id lid -> (problem, tile) -> K loop + epilogue.
-template <int BM, int BN, int WM, int WN, int S, int BK, bool MIX = false>
+// PROX: the launch carries a FedProx term (bt.mu != 0; the launcher picks the instantiation), so the
+// kernels of the default path compile from the code they had before the term existed.
+template <int BM, int BN, int WM, int WN, int S, int BK, bool MIX = false, bool PROX = false>
 DEV void dwb_tile(const DwBatch& bt, int lid, char* smem) {
+  constexpr int EPI = PROX ? EPI_F32P : EPI_F32;
   int i = 0;
   while (i + 1 < bt.n && lid >= bt.pr[i + 1].tile0) ++i;  // block-uniform
   const DwProb& q = bt.pr[i];
@@ -1821,6 +1845,10 @@ DEV void dwb_tile(const DwBatch& bt, int lid, char* smem) {
     p.adam.p = q.p; p.adam.m = q.m; p.adam.v = q.v; p.adam.sh = q.sh; p.adam.step = bt.step;
     p.adam.lr = bt.lr; p.adam.b1 = bt.b1; p.adam.b2 = bt.b2; p.adam.eps = bt.eps; p.adam.wd = q.wd;
     p.adam.decoupled = bt.decoupled;
+    if constexpr (PROX) {
+      p.adam.mu = bt.mu;
+      p.adam.anchor = q.anchor;
+    }
     // A scheduled rate is resolved here, once per thread and outside the K loop (uniform: kept in a
     // scalar register), so the epilogues -- shared with the launches that take a plain rate -- read
     // this step's rate from p.adam.lr.  The constant schedule leaves the rate as it came.
@@ -1832,15 +1860,16 @@ DEV void dwb_tile(const DwBatch& bt, int lid, char* smem) {
       p.acol_p = bt.rest.p + off; p.acol_m = bt.rest.m + off; p.acol_v = bt.rest.v + off;
       p.acol_sh = bt.rest.sh ? bt.rest.sh + off : nullptr;
       p.acol_wd = q.bias_wd;
+      if constexpr (PROX) p.acol_a = bt.rest.anchor ? bt.rest.anchor + off : nullptr;
     }
   }
   if constexpr (MIX) {
     if (q.half) {  // block-uniform
-      gemm_tile<DWB_HBM, DWB_HBN, false, false, EPI_F32, DWB_HWM, DWB_HWN, S, BK>(p, lid - q.tile0, smem);
+      gemm_tile<DWB_HBM, DWB_HBN, false, false, EPI, DWB_HWM, DWB_HWN, S, BK>(p, lid - q.tile0, smem);
       return;
     }
   }
-  gemm_tile<BM, BN, false, false, EPI_F32, WM, WN, S, BK>(p, lid - q.tile0, smem);
+  gemm_tile<BM, BN, false, false, EPI, WM, WN, S, BK>(p, lid - q.tile0, smem);
 }
 
 // Mixed schedule: tile block b (past the rest blocks, whose count is a multiple of 8, so b % 8 is
@@ -1862,15 +1891,17 @@ DEV int dwb_mixed_lid(const DwBatch& bt, int b) {
 // walk the run table (adam_kernel<true, true>'s element body), the others take 64-row flag chunks
 // of the word table per wave (adam_rows_kernel's row body) -- the same arithmetic, bitwise.
 constexpr int DWB_RUNS_LDS = 4096;  // run-table entries (3 per run) staged in LDS by the flat rest blocks
-template <int NT>
+template <int NT, bool PROX>
 DEV void dwb_rest(const DwBatch& bt, int rb, char* smem) {
   const FdAdamRest& r = bt.rest;
   float lr_t, ss, inv;
   adam_bias_corr(bt.step, bt.lr, bt.sched, bt.b1, bt.b2, lr_t, ss, inv);
   AdamArgs a{};
   a.step = bt.step; a.lr = lr_t; a.b1 = bt.b1; a.b2 = bt.b2; a.eps = bt.eps;
+  a.mu = PROX ? bt.mu : 0.f;  // (a constant 0 folds every anchor load away: adam_common.h ld_anchor)
   if (rb < r.flat_blocks) {
     a.p = r.p; a.g = r.g; a.m = r.m; a.v = r.v; a.shadow = reinterpret_cast<bf16_t*>(r.sh);
+    a.anchor = r.anchor;
     a.wd = bt.wd; a.decoupled = bt.decoupled;
     a.runs = r.runs; a.nruns = r.nruns; a.n4 = r.n4;
     a.run_wd = r.run_wd;
@@ -1889,7 +1920,7 @@ DEV void dwb_rest(const DwBatch& bt, int rb, char* smem) {
     for (long long v0 = (long long)rb * NT + threadIdx.x; v0 < r.n4; v0 += U * stride) {
       long long idx[U];
       float wd[U];
-      float4 p4[U], g4[U], m4[U], v4[U];
+      float4 p4[U], g4[U], m4[U], v4[U], a4[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const long long vi = min(v0 + u * stride, r.n4 - 1);
@@ -1903,6 +1934,7 @@ DEV void dwb_rest(const DwBatch& bt, int rb, char* smem) {
         g4[u] = ld_nt(reinterpret_cast<const float4*>(a.g) + idx[u]);
         m4[u] = ld_nt(reinterpret_cast<const float4*>(a.m) + idx[u]);
         v4[u] = ld_nt(reinterpret_cast<const float4*>(a.v) + idx[u]);
+        a4[u] = ld_anchor(a, idx[u]);
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -1910,7 +1942,7 @@ DEV void dwb_rest(const DwBatch& bt, int rb, char* smem) {
         const long long i = idx[u];
         float pp[4] = {p4[u].x, p4[u].y, p4[u].z, p4[u].w}, gg[4] = {g4[u].x, g4[u].y, g4[u].z, g4[u].w};
         float mm[4] = {m4[u].x, m4[u].y, m4[u].z, m4[u].w}, vv[4] = {v4[u].x, v4[u].y, v4[u].z, v4[u].w};
-        adam_math4(a, wd[u], pp, gg, mm, vv, ss, inv);
+        adam_math4(a, wd[u], pp, gg, mm, vv, a4[u], ss, inv);
         st_nt(reinterpret_cast<float4*>(a.p) + i, make_float4(pp[0], pp[1], pp[2], pp[3]));
         st_nt(reinterpret_cast<float4*>(a.m) + i, make_float4(mm[0], mm[1], mm[2], mm[3]));
         st_nt(reinterpret_cast<float4*>(a.v) + i, make_float4(vv[0], vv[1], vv[2], vv[3]));
@@ -1923,6 +1955,7 @@ DEV void dwb_rest(const DwBatch& bt, int rb, char* smem) {
   if (!r.ever) return;
   a.p = r.p + r.woff; a.g = r.g + r.woff; a.m = r.m + r.woff; a.v = r.v + r.woff;
   a.shadow = r.sh ? reinterpret_cast<bf16_t*>(r.sh) + r.woff : nullptr;
+  a.anchor = r.anchor ? r.anchor + r.woff : nullptr;
   a.wd = r.wwd; a.decoupled = bt.decoupled;  // (wwd != 0: decoupled only, the other rows decay lazily)
   a.touched = r.ever; a.now = r.now;
   const int lane = threadIdx.x & 63;
@@ -1938,7 +1971,7 @@ constexpr int dwb_smem() {
   return MIX && H::SMEM > G::SMEM ? H::SMEM : G::SMEM;
 }
 
-template <int BM, int BN, int WM, int WN, int S, int BK = BKT, bool MIX = false>
+template <int BM, int BN, int WM, int WN, int S, int BK = BKT, bool MIX = false, bool PROX = false>
 __global__ __launch_bounds__(64 * WM * WN, 2) void gemm_dw_batch_kernel(DwBatch bt) {
   constexpr int SMEM = dwb_smem<BM, BN, WM, WN, S, BK, MIX>();
   static_assert(SMEM <= LDS_MAX, "LDS");
@@ -1951,25 +1984,25 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void gemm_dw_batch_kernel(DwBatch 
   int bid = blockIdx.x;
   if (bt.rest.first) {
     if (bid < nrest) {  // block-uniform
-      dwb_rest<64 * WM * WN>(bt, bid, smem);
+      dwb_rest<64 * WM * WN, PROX>(bt, bid, smem);
       return;
     }
     bid -= nrest;
   } else {
     const int nblk = MIX && bt.mixed ? 8 * (bt.cls_pad[0] + bt.cls_pad[1] + bt.cls_pad[2]) : bt.ntiles;
     if (bid >= nblk) {
-      dwb_rest<64 * WM * WN>(bt, bid - nblk, smem);
+      dwb_rest<64 * WM * WN, PROX>(bt, bid - nblk, smem);
       return;
     }
   }
   if constexpr (MIX) {
     if (bt.mixed) {
       const int lid = dwb_mixed_lid(bt, bid);
-      if (lid >= 0) dwb_tile<BM, BN, WM, WN, S, BK, true>(bt, lid, smem);
+      if (lid >= 0) dwb_tile<BM, BN, WM, WN, S, BK, true, PROX>(bt, lid, smem);
       return;
     }
   }
-  dwb_tile<BM, BN, WM, WN, S, BK>(bt, xcd_remap(bid, bt.ntiles), smem);
+  dwb_tile<BM, BN, WM, WN, S, BK, false, PROX>(bt, xcd_remap(bid, bt.ntiles), smem);
 }
 
 // out[i] = (accumulate ? out[i] : 0) + sum_z slab[z][i]   (deterministic split-K reduce)
@@ -2554,6 +2587,14 @@ bool dwb_launch_cfg(int id, DwBatch& bt, hipStream_t st, bool dry) {
     return true;
   };
   if (bt.mixed && id != 11) return false;
+  if (bt.mu != 0.f) {  // the FedProx arm of each configuration (the same tiles, anchors in the epilogues)
+    switch (id) {
+      case 1: return go(gemm_dw_batch_kernel<128, 128, 2, 2, 2, BKT, false, true>, 128, 128, 256);
+      case 8: return go(gemm_dw_batch_kernel<128, 64, 2, 2, 2, BKT, false, true>, 128, 64, 256);
+      case 11: return go(gemm_dw_batch_kernel<256, 256, 2, 4, 2, BKT, true, true>, 256, 256, 512);
+    }
+    return false;
+  }
   switch (id) {
     case 1: return go(gemm_dw_batch_kernel<128, 128, 2, 2, 2>, 128, 128, 256);
     case 8: return go(gemm_dw_batch_kernel<128, 64, 2, 2, 2>, 128, 64, 256);
@@ -2666,9 +2707,19 @@ bool plan_dwb_mix(DwBatch& bt, int mode) {
 }
 
 int fd_gemm_dw_batch(int n, const DwProb* probs, int K, const int* step, const float* hyper, int cfg,
-                     const FdAdamRest* rest, const FdLrSched* sched, hipStream_t st) {
+                     const FdAdamRest* rest, const FdLrSched* sched, float prox_mu, hipStream_t st) {
   if (n <= 0 || n > DWB_MAXP || K <= 0 || K % BKT) return 1;
+  // FedProx (adam_elem): a proximal term needs the fused Adam and an anchor beside every state it
+  // updates -- each problem's, and the arena's with the rest of the step (where a decaying sparse
+  // word table is refused: its rows without state drift from their anchors)
+  if (!(prox_mu >= 0.f) || !std::isfinite(prox_mu) || (prox_mu != 0.f && !hyper)) return 9;
+  if (prox_mu != 0.f) {
+    for (int i = 0; i < n; ++i)
+      if (probs[i].p && !probs[i].anchor) return 9;
+    if (rest && rest->p && (!rest->anchor || (rest->ever && rest->wwd != 0.f))) return 9;
+  }
   DwBatch bt{};
+  bt.mu = prox_mu;
   if (rest && rest->p) {
     if (!hyper || !step || !rest->g || !rest->m || !rest->v || (rest->nruns > 0) != (rest->runs != nullptr) ||
         rest->n4 < 0 || (rest->ever && (rest->wrows <= 0 || rest->wrow4 <= 0 || rest->woff % 4)))

@@ -15,6 +15,7 @@
 // the reference's four host syncs per eval batch.
 #include "common.h"
 
+#include <cmath>
 #include <cstdlib>
 
 namespace {
@@ -342,16 +343,22 @@ int fd_eval_metrics(const float* logits, const long long* labels, int B, double*
 int fd_adam(float* p, const float* g, float* m, float* v, void* shadow, long long n, const int* step, float lr,
             float b1, float b2, float eps, float wd, int decoupled, const unsigned char* touched,
             const unsigned char* now, long long skip_off, long long skip_rows, int row_len, const long long* runs,
-            int nruns, long long run_total4, const float* run_wd, const FdLrSched* sched, hipStream_t st) {
+            int nruns, long long run_total4, const float* run_wd, const FdLrSched* sched, float prox_mu,
+            const float* anchor, hipStream_t st) {
   if (n % 4 != 0 || skip_off % 4 != 0 || row_len % 4 != 0) return 1;
+  // FedProx (adam_elem): anchor is laid out like p.  Skipping untouched rows stays exact under it
+  // without weight decay: such a row equals its anchor, so its proximal gradient is mu * (+0).
+  if (!(prox_mu >= 0.f) || !std::isfinite(prox_mu) || (prox_mu != 0.f && !anchor)) return 6;
   // skipping untouched rows is exact without weight decay; with decoupled decay the caller owes
   // those rows their multiplications (fd_adam_lazy_decay)
   if (wd != 0.f && touched && !decoupled) return 3;
+  // (a decaying row without state drifts from its anchor: nothing can be skipped then)
+  if (prox_mu != 0.f && wd != 0.f && touched) return 7;
   if (run_wd && (touched || !runs)) return 5;
   if (runs && (nruns <= 0 || run_total4 <= 0)) return 4;
   AdamArgs a{p, g, m, v, (bf16_t*)shadow, runs ? run_total4 : n / 4, step, lr, b1, b2, eps, wd, decoupled,
              skip_off / 4, (skip_off + skip_rows * row_len) / 4, row_len / 4, touched, now, runs, nruns, run_wd,
-             sched ? *sched : FdLrSched{}};
+             anchor, prox_mu, sched ? *sched : FdLrSched{}};
   const int grid = grid_for(n / 4);
   // FD_ADAM_NT: 0 = default cache policy, 1 = nontemporal g/m/v, 2 = also the fp32 master (default:
   // 2.336 vs 2.366-2.387 ms/step, profiles/r1_ab_adam_nt_master.txt -- only the bf16 shadow is re-read soon)
@@ -369,11 +376,16 @@ int fd_adam(float* p, const float* g, float* m, float* v, void* shadow, long lon
 // decoupled: the unflagged rows' decay is applied lazily, fd_adam_lazy_decay).
 int fd_adam_rows(float* p, const float* g, float* m, float* v, void* shadow, int rows, int row_len, const int* step,
                  float lr, float b1, float b2, float eps, const unsigned char* ever, const unsigned char* now,
-                 float wd, int decoupled, const FdLrSched* sched, hipStream_t st) {
+                 float wd, int decoupled, const FdLrSched* sched, float prox_mu, const float* anchor,
+                 hipStream_t st) {
   if (row_len % 4 != 0 || rows <= 0 || !ever) return 1;
   if (wd != 0.f && !decoupled) return 3;
+  // FedProx: anchor is the table's, laid out like p; exact while the table does not decay (a row
+  // without state equals its anchor), refused when it does
+  if (!(prox_mu >= 0.f) || !std::isfinite(prox_mu) || (prox_mu != 0.f && !anchor)) return 6;
+  if (prox_mu != 0.f && wd != 0.f) return 7;
   AdamArgs a{p, g, m, v, (bf16_t*)shadow, 0, step, lr, b1, b2, eps, wd, decoupled, 0, 0, row_len / 4, ever, now,
-             nullptr, 0, nullptr, sched ? *sched : FdLrSched{}};
+             nullptr, 0, nullptr, anchor, prox_mu, sched ? *sched : FdLrSched{}};
   hipLaunchKernelGGL(adam_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, a, rows, row_len / 4);  // wave per row
   return 0;
 }

@@ -149,6 +149,7 @@ def _virtual(argv):
             "clients": [{"client": c["client"], "local_test": c["local_test"], "aggregated_test": c["aggregated_test"],
                          "epoch_losses": c["train"]["epoch_losses"], "train_steps": c["train"]["steps"],
                          "rel_l2_local_to_aggregate": c["rel_l2_local_to_aggregate"],
+                         "l2_local_to_start": c["l2_local_to_start"],
                          **({"teacher_test": c["teacher_test"]} if "teacher_test" in c else {})}
                         for c in h["clients"]]})
     if cfg.save_checkpoints:

@@ -27,7 +27,8 @@ class FedConfig:
     data_profile: str = "default"
     data_fraction: float = 0.1              # client1.py:23
     base_seed: int = 42                     # client1.py:89 (client2.py:84 uses 43)
-    partition: str = "iid_overlap"          # "iid_overlap" (reference) | "disjoint"
+    partition: str = "iid_overlap"          # "iid_overlap" (reference) | "disjoint" | "label_skew" (non-IID)
+    partition_skew: float = 0.9             # label_skew: DDoS share of even clients (odd: 1 - it); in [0.5, 1)
     max_len: int = 128                      # client1.py:27
     # --- model (client1.py:53-65) ---------------------------------------------------
     model_path: Optional[str] = None        # optional HF distilbert dir; None -> random init
@@ -52,6 +53,9 @@ class FedConfig:
     # "round": every round's fresh Adam restarts the ramp over that round's steps;
     # "run": one ramp over rounds x steps per round (round r starts at offset r x steps per round)
     lr_schedule_scope: str = "round"
+    # FedProx (engine/optim.py): mu / 2 * ||w - w_global||^2 added to every client's loss, w_global the
+    # round's starting weights -- holds local epochs on a skewed shard near the global model.  0: off
+    prox_mu: float = 0.0
     impl: str = "auto"                      # "hip" | "torch" | "auto" (hip on GPU)
     use_graph: bool = True                  # capture the train step in a HIP graph
     # --- federation (server.py:10-13) -------------------------------------------------

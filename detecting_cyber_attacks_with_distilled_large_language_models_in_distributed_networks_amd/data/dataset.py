@@ -142,27 +142,59 @@ class ClientData:
     n_rows: int
 
 
-def build_client_data(frame, client_id: int, data_fraction: float = 0.1, base_seed: int = 42, max_len: int = 128,
-                      tokenizer: Optional[WordPieceTokenizer] = None, partition: str = "iid_overlap",
-                      num_clients: int = 1, log=None) -> ClientData:
-    """Client k's 60/20/20 splits (client1.py:363-369 with seed 42 + k).
+def check_partition_skew(skew: float) -> float:
+    """The ``label_skew`` partition's majority share: in [0.5, 1)."""
+    if not 0.5 <= skew < 1.0:
+        raise ValueError(f"partition_skew must lie in [0.5, 1), got {skew}")
+    return float(skew)
+
+
+def partition_rows(df, client_id: int, data_fraction: float = 0.1, seed: int = 42, partition: str = "iid_overlap",
+                   num_clients: int = 1, partition_skew: float = 0.9):
+    """Client ``client_id``'s rows of the cleaned frame ``df`` (in training order), sampled with
+    ``seed`` (the client's own: base seed + client id).
 
     ``iid_overlap`` (reference): each client samples ``data_fraction`` of the full
     frame independently with its own seed -> ~10 % row overlap between clients.
     ``disjoint``: rows are first dealt round-robin to clients by a seed-0 permutation.
+    ``label_skew``: as many rows as ``iid_overlap`` draws, but a share ``partition_skew`` of them
+    is DDoS for even clients and ``1 - partition_skew`` for odd ones (non-IID sites: one sees mostly
+    attacks, its neighbour mostly benign flows).  Each class is sampled without replacement, then
+    the two are concatenated and shuffled, all with the client's seed.
     """
-    from .featurize import clean_frame, render_texts, split_60_20_20
-    seed = base_seed + client_id
-    if log:
-        log("Starting data preprocessing")
-    df = clean_frame(frame) if isinstance(frame, __import__("pandas").DataFrame) else frame
+    if partition == "label_skew":
+        skew = check_partition_skew(partition_skew)
+        n = int(round(data_fraction * len(df)))  # (DataFrame.sample(frac=)'s count)
+        n_ddos = int(round((skew if client_id % 2 == 0 else 1.0 - skew) * n))
+        is_ddos = (df["Label"] == "DDoS").to_numpy()
+        parts = []
+        for name, rows, want in (("DDoS", df[is_ddos], n_ddos), ("benign", df[~is_ddos], n - n_ddos)):
+            if want > len(rows):
+                raise ValueError(f"label_skew partition: client {client_id} needs {want} {name} rows "
+                                 f"(partition_skew {skew}, {n} rows per client) but the data has {len(rows)}")
+            parts.append(rows.sample(n=want, random_state=seed))
+        pd = __import__("pandas")
+        return pd.concat(parts).sample(frac=1.0, random_state=seed)
     if partition == "disjoint" and num_clients > 1:
         order = np.random.default_rng(0).permutation(len(df))
         df = df.iloc[order[client_id::num_clients]]
         frac = min(1.0, data_fraction * num_clients)
     else:
         frac = data_fraction
-    df = df.sample(frac=frac, random_state=seed)
+    return df.sample(frac=frac, random_state=seed)
+
+
+def build_client_data(frame, client_id: int, data_fraction: float = 0.1, base_seed: int = 42, max_len: int = 128,
+                      tokenizer: Optional[WordPieceTokenizer] = None, partition: str = "iid_overlap",
+                      num_clients: int = 1, log=None, partition_skew: float = 0.9) -> ClientData:
+    """Client k's 60/20/20 splits (client1.py:363-369 with seed 42 + k) of its rows
+    (``partition_rows``)."""
+    from .featurize import clean_frame, render_texts, split_60_20_20
+    seed = base_seed + client_id
+    if log:
+        log("Starting data preprocessing")
+    df = clean_frame(frame) if isinstance(frame, __import__("pandas").DataFrame) else frame
+    df = partition_rows(df, client_id, data_fraction, seed, partition, num_clients, partition_skew)
     texts = render_texts(df)
     labels = (df["Label"].to_numpy() == "DDoS").astype(np.int64).tolist()
     if log:

@@ -74,7 +74,26 @@ The sparse word-embedding table under weight decay:
    clients (fed/runner.py) -- all run after ``train_model`` has returned, i.e. after a flush; code
    that reads ``arena.master`` between the steps of its own loop calls ``finish()`` first;
 3. coupled (L2) decay, word table decays: the gradient ``wd * p`` is non-zero for every row, so
-   nothing can be skipped -- the dense word gradient and the dense table update, as before.
+   nothing can be skipped -- the dense word gradient and the dense table update, as before;
+4. a proximal term (``prox_mu > 0``, below) and the word table decays, coupled or decoupled: a row
+   without state decays away from its anchor, so its proximal gradient is non-zero and nothing can
+   be skipped either -- the dense path, as in 3 (``dense_word_decay()``).
+
+FedProx (Li et al., 2020).  ``prox_mu > 0`` adds ``mu / 2 * ||w - w_global||^2`` to the local
+objective: every gradient gets ``mu * (p - anchor)`` -- taken from the parameter as loaded, before a
+decoupled decay multiplies it -- i.e. ``p.grad += mu * (p - p_global)`` followed by
+``torch.optim.Adam`` / ``AdamW.step()``.  One scalar for the whole model (biases and LayerNorms
+included).  The term lives in the shared element function (csrc/kernels/adam_common.h adam_elem),
+so every launch that applies Adam applies it -- the fused weight-gradient epilogues, whose gradient
+never exists in memory, included -- and fused and unfused steps stay bitwise equal.  ``anchor`` is
+an fp32 copy of the master arena, allocated once (captured graphs keep its address) and re-snapshot
+in place only by ``reset_state()``, which the federated runner calls with each round's starting
+weights loaded; the same call clears the word table's row flags, hence the invariant *a word row
+without Adam state equals its anchor*: its proximal gradient is ``mu * (+0)`` and its whole step
+exactly zero, so the row-flag skip (cases 1 and "no decay") stays exact with no lazy machinery.  The
+anchor is only read when ``prox_mu != 0`` (+4 B per parameter per step); with ``prox_mu == 0``
+nothing changes, bit for bit.  The per-layer fused launches (``linear_dw`` / ``linear_dw2``) refuse
+a proximal term as they refuse a schedule.
 
 Learning-rate schedules.  ``schedule="linear"`` is HF ``get_linear_schedule_with_warmup`` (the rate
 rises from 0 over ``warmup_steps`` steps, then falls to 0 at ``total_steps``; the first step of a
@@ -119,17 +138,23 @@ def check_schedule(schedule: str, warmup_steps: int, total_steps: int, step_offs
 
 class FusedHyper(list):
     """``fused_args``'s hyper-parameters [lr, b1, b2, eps, wd, decoupled] with the schedule that lr is
-    the base rate of (``sched``: None, or the launches' (kind, warmup, total, offset))."""
+    the base rate of (``sched``: None, or the launches' (kind, warmup, total, offset)) and the FedProx
+    term (``prox``: None, or (mu, the anchor laid out like the master arena))."""
     sched = None
+    prox = None
 
 
 class ArenaAdam:
     def __init__(self, model, lr: float = 2e-5, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, decoupled: bool = False, overlap: bool = False,
                  fuse_dw: bool = True, no_decay=(), schedule: str = "constant", warmup_steps: int = 0,
-                 total_steps: int = 0, step_offset: int = 0, warmup_ratio: float = 0.0):
+                 total_steps: int = 0, step_offset: int = 0, warmup_ratio: float = 0.0, prox_mu: float = 0.0):
         if not (math.isfinite(weight_decay) and weight_decay >= 0.0):
             raise ValueError(f"weight_decay must be finite and >= 0, got {weight_decay}")
+        if not (math.isfinite(prox_mu) and prox_mu >= 0.0):
+            raise ValueError(f"prox_mu must be finite and >= 0, got {prox_mu}")
+        self.prox_mu = float(prox_mu)
+        self.anchor = None
         if not math.isfinite(lr):
             raise ValueError(f"lr must be finite, got {lr}")
         if not 0.0 <= warmup_ratio <= 1.0:
@@ -156,8 +181,10 @@ class ArenaAdam:
         if prev is not None and prev is not self:
             prev.finish()  # (an earlier optimizer of this model may still owe its rows their decay)
         self._dense_word = False
-        if self.word_wd != 0.0 and not decoupled:
-            self.dense_word_decay()  # L2 decay reaches every row: keep the dense word gradient
+        if self.word_wd != 0.0 and (not decoupled or self.prox_mu != 0.0):
+            # L2 decay reaches every row, and under a proximal term a decaying row without state
+            # drifts from its anchor: keep the dense word gradient
+            self.dense_word_decay()
         self._alloc()
         if hasattr(model, "word_embedding_span"):
             model._lazy_decay_opt = weakref.ref(self)
@@ -325,6 +352,9 @@ class ArenaAdam:
         dev = self.arena.device
         self.m = torch.zeros_like(self.arena.master)
         self.v = torch.zeros_like(self.arena.master)
+        # FedProx anchor: the round's starting weights.  Allocated once (captured graphs keep its
+        # address) and only ever re-snapshot in place, by reset_state()
+        self.anchor = self.arena.master.clone() if self.prox_mu != 0.0 else None
         self.step_t = torch.zeros(1, dtype=torch.int32, device=dev)
         self.row_step = None  # lazy decay: steps whose decay each word row without state has received
         if dev.type == "cuda" and hasattr(self.model, "word_embedding_span"):
@@ -363,20 +393,28 @@ class ArenaAdam:
             else:
                 K.step_inc(None, seed)
 
+    def prox_args(self, sl: Optional[slice] = None):
+        """The ``prox=`` argument of the Adam launches: None (no proximal term) or (mu, anchor) with
+        the anchor of the whole arena, or of its elements ``sl``."""
+        if self.prox_mu == 0.0:
+            return None
+        return (self.prox_mu, self.anchor if sl is None else self.anchor[sl])
+
     def _update(self, off: int, n: int, sparse: bool):
         from ..ops import kernels as K
         A = self.arena
         b1, b2 = self.betas
         sl = slice(off, off + n)
         wd = self._span_decay(off, n) if self.grouped_decay else self.weight_decay
+        prox = self.prox_args(sl)
         if sparse:
             woff, rows, rl = self.model.word_embedding_span()
             K.adam(A.master[sl], A.grad[sl], self.m[sl], self.v[sl], A.shadow[sl], self.step_t, self.lr, b1, b2,
                    self.eps, wd, self.decoupled, self.model.emb_ever, self.model.emb_now, woff - off,
-                   rows, rl, sched=self.sched_args())
+                   rows, rl, sched=self.sched_args(), prox=prox)
         else:
             K.adam(A.master[sl], A.grad[sl], self.m[sl], self.v[sl], A.shadow[sl], self.step_t, self.lr, b1, b2,
-                   self.eps, wd, self.decoupled, sched=self.sched_args())
+                   self.eps, wd, self.decoupled, sched=self.sched_args(), prox=prox)
 
     def _on_layer_grads(self, i: int):
         """Backward hook: block i's gradients are final -> update it on the side stream."""
@@ -425,6 +463,7 @@ class ArenaAdam:
         b1, b2 = self.betas
         hp = FusedHyper([self.lr, b1, b2, self.eps, self.weight_decay, 1.0 if self.decoupled else 0.0])
         hp.sched = self.sched_args()
+        hp.prox = self.prox_args()
         return st, hp
 
     def _runs_table(self, runs):
@@ -470,6 +509,10 @@ class ArenaAdam:
         self._rest_in_launch = False
         if getattr(self.model, "emb_ever", None) is not None:
             self.model.emb_ever.zero_()
+        if self.anchor is not None:
+            # the round's starting weights, in place (after finish(): the settled master), and in
+            # the same call that clears the row flags: a word row without state equals its anchor
+            self.anchor.copy_(self.arena.master)
 
     def zero_grad(self, set_to_none: bool = False):
         self.model.zero_grad()
@@ -593,12 +636,12 @@ class ArenaAdam:
                 sl = slice(woff, wend)
                 K.adam_rows(A.master[sl], A.grad[sl], self.m[sl], self.v[sl], A.shadow[sl], self.step_t, self.lr, b1,
                             b2, self.eps, self.model.emb_ever, self.model.emb_now, rl, self.word_wd, self.decoupled,
-                            sched=sc)
+                            sched=sc, prox=self.prox_args(sl))
                 rest_table = self._runs_table(rest) if len(rest) > 1 else None
                 if rest_table is not None:
                     K.adam(A.master, A.grad, self.m, self.v, A.shadow, self.step_t, self.lr, b1, b2, self.eps,
                            self.weight_decay, self.decoupled, runs=rest_table, run_decay=self._runs_decay(rest),
-                           sched=sc)
+                           sched=sc, prox=self.prox_args())
                 else:
                     for off, n in rest:
                         self._update(off, n, False)
@@ -606,7 +649,8 @@ class ArenaAdam:
                 from ..ops import kernels as K
                 b1, b2 = self.betas
                 K.adam(A.master, A.grad, self.m, self.v, A.shadow, self.step_t, self.lr, b1, b2, self.eps,
-                       self.weight_decay, self.decoupled, runs=table, run_decay=self._runs_decay(runs), sched=sc)
+                       self.weight_decay, self.decoupled, runs=table, run_decay=self._runs_decay(runs), sched=sc,
+                       prox=self.prox_args())
             else:
                 for off, n in runs:
                     self._update(off, n, sparse and off <= woff < off + n)
@@ -621,6 +665,8 @@ class ArenaAdam:
         self.step_t += 1
         lr = self.lr_at(t)
         p, g = A.master, A.grad
+        if self.prox_mu != 0.0:  # FedProx: from p as it is, before a decoupled decay multiplies it
+            g = g + self.prox_mu * (p - self.anchor)
         if self.weight_decay and self.grouped_decay:  # one group per segment, as torch.optim's param groups
             if not self.decoupled:
                 g = g.clone()
@@ -653,6 +699,8 @@ class ArenaAdam:
             sd["schedule"] = {"name": self.schedule, "warmup_steps": self.warmup_steps,
                               "warmup_ratio": self.warmup_ratio, "total_steps": self.total_steps,
                               "step_offset": self.step_offset}
+        if self.prox_mu != 0.0:  # (the anchor is not saved: a resumed job restarts at a round boundary)
+            sd["prox_mu"] = self.prox_mu
         return sd
 
     def load_state_dict(self, sd):

@@ -59,16 +59,21 @@ def make_optimizer(model, cfg: FedConfig, round_index: int = 0, rounds: int = 1,
                    steps_per_round: Optional[int] = None) -> ArenaAdam:
     """The client optimizer of a run: Adam / AdamW with the configuration's hyper-parameters, its
     no-decay parameter group (``--no-decay bias,LayerNorm,layer_norm``) and its learning-rate
-    schedule (``_schedule_kwargs``; round_index / rounds / steps_per_round matter to scope "run")."""
+    schedule (``_schedule_kwargs``; round_index / rounds / steps_per_round matter to scope "run"),
+    and the FedProx term (``--prox-mu``).  Its anchor is the model's weights when the optimizer's
+    ``reset_state()`` runs: every caller builds the optimizer and resets it with the round's starting
+    weights loaded (the broadcast init, the aggregate a resumed job loads, or the last round's
+    aggregate -- which a client dropped from that round's average receives too)."""
     return ArenaAdam(model, lr=cfg.lr, betas=cfg.betas, eps=cfg.eps, weight_decay=cfg.weight_decay,
-                     decoupled=cfg.decoupled_weight_decay,
+                     decoupled=cfg.decoupled_weight_decay, prox_mu=cfg.prox_mu,
                      no_decay=tuple(x.strip() for x in cfg.no_decay.split(",") if x.strip()),
                      **_schedule_kwargs(cfg, round_index, rounds, steps_per_round))
 
 
 def make_teacher_optimizer(teacher, cfg: FedConfig) -> ArenaAdam:
     """The teacher's plain Adam; with a configured schedule, the same schedule over the teacher's
-    own step count (``train_model`` fills in the total)."""
+    own step count (``train_model`` fills in the total).  No proximal term: the teachers stay local,
+    there is no global teacher to stay near."""
     if cfg.lr_schedule == "constant":
         return ArenaAdam(teacher, lr=cfg.lr)
     return ArenaAdam(teacher, lr=cfg.lr, **_schedule_kwargs(cfg))
@@ -111,7 +116,8 @@ class FederatedClient:
                     self.frame = generate_cicids2017(cfg.synthetic_rows, seed=0, profile=cfg.data_profile)
             self.tokenizer = WordPieceTokenizer.from_pretrained(cfg.model_path)
             self.data = build_client_data(self.frame, self.idx, cfg.data_fraction, cfg.base_seed, cfg.max_len,
-                                          self.tokenizer, cfg.partition, self.num_clients, log=log)
+                                          self.tokenizer, cfg.partition, self.num_clients, log=log,
+                                          partition_skew=cfg.partition_skew)
         dev = self.device
         self.train_loader = DeviceLoader(self.data.train, cfg.batch_size, shuffle=True, device=dev,
                                          seed=cfg.client_seed(self.idx))
@@ -471,7 +477,7 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
     cs = []
     for v in range(n_clients):
         data = build_client_data(client.frame, v, cfg.data_fraction, cfg.base_seed, cfg.max_len, client.tokenizer,
-                                 cfg.partition, n_clients)
+                                 cfg.partition, n_clients, partition_skew=cfg.partition_skew)
         cs.append({"data": data,
                    "loader": DeviceLoader(data.train, cfg.batch_size, shuffle=True, device=dev,
                                           seed=cfg.client_seed(v)),
@@ -519,6 +525,8 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
             local = _metrics_record(evaluate_model(model, test, name=f"Client {v + 1} local test"))
             locals_.append(A.master.detach().clone())
             rec.update({"train": tr, "train_wall_s": time.perf_counter() - t0, "local_test": local})
+            # client drift: how far the local epochs moved this client from the round's start
+            rec["l2_local_to_start"] = float((locals_[-1] - glob).norm())
             recs.append(rec)
             del opt
             say(f"round {r + 1}/{rounds} client {v + 1}/{n_clients}: local acc {local['accuracy']:.3f} % "

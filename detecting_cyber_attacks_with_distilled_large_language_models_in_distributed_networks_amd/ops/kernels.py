@@ -150,10 +150,15 @@ def linear_dx(dy: torch.Tensor, w: torch.Tensor, gelu_u: Optional[torch.Tensor] 
 
 
 def _no_sched(hp, what: str):
-    """The per-layer fused dW launches take a plain rate: refuse a scheduled optimizer's
-    hyper-parameters (``FusedHyper.sched``) instead of training at its base rate."""
+    """The per-layer fused dW launches take a plain rate and no proximal term: refuse a scheduled
+    optimizer's hyper-parameters (``FusedHyper.sched``) instead of training at its base rate, and a
+    FedProx optimizer's (``FusedHyper.prox``) instead of dropping the term."""
     if getattr(hp, "sched", None) is not None:
         raise ValueError(f"{what}: the fused Adam of this launch takes no learning-rate schedule "
+                         "(use the all-layer launch, linear_dw_batch)")
+    # ... nor a FedProx proximal term (``FusedHyper.prox``)
+    if getattr(hp, "prox", None) is not None:
+        raise ValueError(f"{what}: the fused Adam of this launch takes no proximal term "
                          "(use the all-layer launch, linear_dw_batch)")
 
 
@@ -208,7 +213,7 @@ ADAM_IN_DW = _os.environ.get("FD_ADAM_IN_DW", "1") != "0"
 DWB_ORDER = int(_os.environ.get("FD_DWB_ORDER", "0"))
 
 
-def linear_dw_batch(jobs: list, adam=None, cfg: int = -1, opt=None, sched=None):
+def linear_dw_batch(jobs: list, adam=None, cfg: int = -1, opt=None, sched=None, prox=None):
     """Every weight gradient of a backward in one launch per 32 problems: for each job
     (dy [K, M], x [K, N], out [M, N] fp32, accumulate[, bias]) out (+)= dy^T x, and the
     optional fp32 [M] bias (+)= the column sums of dy (``DW_QKV_BIAS``).  No split-K: each
@@ -217,9 +222,16 @@ def linear_dw_batch(jobs: list, adam=None, cfg: int = -1, opt=None, sched=None):
     step to each finished gradient tile instead of storing it.  opt (with adam): the optimizer
     (``ArenaAdam``) -- the last launch also runs the rest of its step (``ADAM_IN_DW``).
     sched (with adam): the learning-rate schedule (kind, warmup, total, offset) whose base rate the
-    hyper-parameters carry; None: the one they name themselves (``FusedHyper.sched``)."""
+    hyper-parameters carry; None: the one they name themselves (``FusedHyper.sched``).
+    prox (with adam): the FedProx term (mu, anchor) of the fused step -- every gradient gets
+    mu * (p - anchor); None: the one the hyper-parameters name (``FusedHyper.prox``).  anchor: a list
+    with one fp32 tensor per job, laid out like its ``out``, or ONE tensor laid out like the master
+    arena of ``opt``, whose views the fused state's offsets select (and which the rest of the step
+    takes whole)."""
     if DWB_ORDER == 1 and len(jobs) <= DW_BATCH_MAX:
         jobs = jobs[::-1]  # (forward block order: the pruned block's problems last)
+        if prox is not None and not isinstance(prox[1], torch.Tensor):
+            prox = (prox[0], list(prox[1])[::-1])  # (per-job anchors follow their jobs)
     starts = list(range(0, len(jobs), DW_BATCH_MAX))
     for i in starts:
         chunk = jobs[i:i + DW_BATCH_MAX]
@@ -233,6 +245,22 @@ def linear_dw_batch(jobs: list, adam=None, cfg: int = -1, opt=None, sched=None):
         sc = sched if sched is not None else getattr(hp, "sched", None)
         if adam is not None and sc is not None:
             extra["sched"] = _sched(sc)
+        px = prox if prox is not None else getattr(hp, "prox", None)
+        if adam is None:
+            px = None
+        if px is not None:
+            mu, anc = px
+            if isinstance(anc, torch.Tensor):  # laid out like the master arena
+                if opt is None:
+                    raise ValueError("linear_dw_batch: an arena-wide anchor needs opt= (whose master arena it mirrors)")
+                base, esz = opt.arena.master.data_ptr(), opt.arena.master.element_size()
+                anchors = []
+                for k in range(len(chunk)):
+                    off = (st[4 * k].data_ptr() - base) // esz
+                    anchors.append(anc[off:off + st[4 * k].numel()])
+            else:
+                anchors = list(anc[i:i + len(chunk)])
+            extra["prox_mu"], extra["anchor"] = float(mu), anchors
         if adam is not None and opt is not None and ADAM_IN_DW and i == starts[-1]:
             # the qkv biases summed by this launch are updated by its tiles when it also finishes
             # the step: mark them, then hand the rest of the step to the launch
@@ -246,6 +274,10 @@ def linear_dw_batch(jobs: list, adam=None, cfg: int = -1, opt=None, sched=None):
                 if groups:
                     extra["bias_decay"] = [opt.decays_of([b])[0] if b is not None else 0.0 for b in bias]
                 extra.update(opt.rest_decay_args())
+                if px is not None:
+                    if not isinstance(px[1], torch.Tensor):
+                        raise ValueError("linear_dw_batch: the rest of the step needs the arena-wide anchor")
+                    extra["anchor"] = extra["anchor"] + [px[1]]
         if any(b is not None for b in bias):
             none = torch.empty(0, dtype=torch.float32, device=outs[0].device)
             bias = [b if b is not None else none for b in bias]
@@ -1027,7 +1059,7 @@ def lr_schedule_table(lr, sched, n):
 
 
 def adam(p, g, m, v, shadow, step, lr, b1, b2, eps, wd, decoupled, touched=None, now=None, skip_off=0, skip_rows=0,
-         row_len=4, runs=None, run_decay=None, sched=None):
+         row_len=4, runs=None, run_decay=None, sched=None, prox=None):
     """Flat-arena Adam.  touched/now (uint8 row flags over [skip_off, skip_off+skip_rows*row_len)) let
     the kernel skip rows with zero state and zero gradient (exact for weight_decay == 0; with
     decoupled decay the caller owes those rows ``adam_lazy_decay``).
@@ -1035,18 +1067,29 @@ def adam(p, g, m, v, shadow, step, lr, b1, b2, eps, wd, decoupled, touched=None,
     update only those element runs, in one launch.  run_decay = (device fp32 [n], the same values
     as a list) from ``adam_run_decay``: a weight decay per run (parameter groups) instead of wd.
     sched = (kind, warmup, total, offset): ``lr`` is the base rate of that schedule, evaluated on
-    the device from ``step`` (None: constant)."""
+    the device from ``step`` (None: constant).
+    prox = (mu, anchor): the FedProx term -- every gradient gets ``mu * (p - anchor)`` (anchor: fp32,
+    laid out like p; read only when mu != 0).  None: no term.  Skipping rows without state stays
+    exact under it while those rows do not decay (they equal their anchors)."""
     table, total4, end4 = runs if runs is not None else (None, 0, 0)
     rwd, rwd_host = run_decay if run_decay is not None else (None, [])
     ext().adam(p, g, m, v, shadow, step, lr, b1, b2, eps, wd, decoupled, touched, now, skip_off, skip_rows, row_len,
-               table, total4, end4, rwd, rwd_host, _sched(sched))
+               table, total4, end4, rwd, rwd_host, _sched(sched), *_prox(prox))
 
 
-def adam_rows(p, g, m, v, shadow, step, lr, b1, b2, eps, ever, now, row_len, wd=0.0, decoupled=False, sched=None):
+def _prox(prox):
+    """prox=None or (mu, anchor) -> the binding's (prox_mu, anchor)."""
+    return (0.0, None) if prox is None else (float(prox[0]), prox[1])
+
+
+def adam_rows(p, g, m, v, shadow, step, lr, b1, b2, eps, ever, now, row_len, wd=0.0, decoupled=False, sched=None,
+              prox=None):
     """Adam over the rows of one [rows][row_len] table (views of the arenas) whose ``ever`` flag
     is set -- the sparse word-embedding update, one wave per 64 row flags.  wd != 0 needs
-    decoupled decay; the rows without state then decay through ``adam_lazy_decay``."""
-    ext().adam_rows(p, g, m, v, shadow, step, lr, b1, b2, eps, ever, now, row_len, wd, decoupled, _sched(sched))
+    decoupled decay; the rows without state then decay through ``adam_lazy_decay``.
+    prox = (mu, anchor of the table): the FedProx term (see ``adam``); wd == 0 only."""
+    ext().adam_rows(p, g, m, v, shadow, step, lr, b1, b2, eps, ever, now, row_len, wd, decoupled, _sched(sched),
+                    *_prox(prox))
 
 
 def adam_lazy_decay(p, shadow, done, ever, step, adj, lr, wd, row_len, ids=None, sched=None):
