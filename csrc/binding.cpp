@@ -148,6 +148,9 @@ int fd_lr_schedule_table(float* out, int n, float lr, const FdLrSched* sched, hi
 int fd_step(int* step, uint32_t* seed, hipStream_t st);
 int fd_scale_cast(float* p, void* shadow, long long n, float scale, hipStream_t st);
 int fd_axpby(float* dst, const float* x, const float* y, float a, float b, long long n, hipStream_t st);
+int fd_server_opt_grid(long long n);
+int fd_server_opt(float* master, float* x, float* m, float* v, void* shadow, long long n, int kind, float inv,
+                  float eta, float b1, float b2, float tau, float* stats, hipStream_t st);
 }
 
 namespace {
@@ -1787,6 +1790,47 @@ void axpby(const at::Tensor& dst, const at::Tensor& x, const c10::optional<at::T
            "axpby");
 }
 
+// The FedOpt server step on the all-reduced sum held in master (head_optim.hip server_opt_kernel):
+// kind 0 avgm (no v), 1 adagrad, 2 adam, 3 yogi; stats (optional) receives two fp32 partial sums
+// per block (sum d^2, sum (x' - x)^2), so it holds at least 2 * grid floats.
+void server_opt(const at::Tensor& master, const at::Tensor& x, const at::Tensor& m,
+                const c10::optional<at::Tensor>& v, const c10::optional<at::Tensor>& shadow, int64_t kind,
+                double inv, double eta, double b1, double b2, double tau, const c10::optional<at::Tensor>& stats) {
+  need(master, at::kFloat, "master");
+  need(x, at::kFloat, "x");
+  need(m, at::kFloat, "m");
+  need_opt(v, at::kFloat, "v");
+  need_opt(shadow, at::kBFloat16, "shadow");
+  need_opt(stats, at::kFloat, "stats");
+  const bool has_v = v.has_value() && v->defined();
+  const bool has_shadow = shadow.has_value() && shadow->defined();
+  const bool has_stats = stats.has_value() && stats->defined();
+  TORCH_CHECK(kind >= 0 && kind <= 3, "server_opt: kind is 0 avgm, 1 adagrad, 2 adam, 3 yogi; got ", kind);
+  TORCH_CHECK(has_v == (kind != 0), "server_opt: v goes with the adaptive kinds, and only with them");
+  const int64_t n = master.numel();
+  TORCH_CHECK(n > 0 && n % 4 == 0, "server_opt: numel % 4");
+  TORCH_CHECK(x.numel() == n && m.numel() == n, "server_opt: x / m sizes");
+  if (has_v) TORCH_CHECK(v->numel() == n, "server_opt: v size");
+  if (has_shadow) TORCH_CHECK(shadow->numel() == n, "server_opt: shadow size");
+  const auto dev = master.device();
+  TORCH_CHECK(x.device() == dev && m.device() == dev && (!has_v || v->device() == dev) &&
+                  (!has_shadow || shadow->device() == dev) && (!has_stats || stats->device() == dev),
+              "server_opt: tensors on one device");
+  TORCH_CHECK(std::isfinite(inv) && inv > 0.0, "server_opt: inv");
+  TORCH_CHECK(std::isfinite(eta) && eta > 0.0, "server_opt: eta > 0");
+  TORCH_CHECK(std::isfinite(tau) && tau > 0.0, "server_opt: tau > 0");
+  TORCH_CHECK(std::isfinite(b1) && b1 >= 0.0 && b1 < 1.0 && std::isfinite(b2) && b2 >= 0.0 && b2 < 1.0,
+              "server_opt: betas in [0, 1)");
+  if (has_stats) TORCH_CHECK(stats->numel() >= 2 * (int64_t)fd_server_opt_grid(n), "server_opt: stats size");
+  check_rc(fd_server_opt(master.data_ptr<float>(), x.data_ptr<float>(), m.data_ptr<float>(), ptr<float>(v),
+                         ptr<void>(shadow), n, (int)kind, (float)inv, (float)eta, (float)b1, (float)b2, (float)tau,
+                         ptr<float>(stats), stream()),
+           "server_opt");
+}
+
+// Blocks of a server_opt launch over n floats (the stats buffer holds two floats per block).
+int64_t server_opt_grid(int64_t n) { return (int64_t)fd_server_opt_grid(n); }
+
 }  // namespace
 
 #ifndef FD_HOST_VALIDATION
@@ -1902,5 +1946,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("step_inc", &step_inc);
   m.def("scale_cast", &scale_cast);
   m.def("axpby", &axpby);
+  m.def("server_opt", &server_opt, py::arg("master"), py::arg("x"), py::arg("m"), py::arg("v"), py::arg("shadow"),
+        py::arg("kind"), py::arg("inv"), py::arg("eta"), py::arg("b1"), py::arg("b2"), py::arg("tau"),
+        py::arg("stats") = py::none());
+  m.def("server_opt_grid", &server_opt_grid);
 }
 #endif  // FD_HOST_VALIDATION

@@ -662,6 +662,26 @@ int fd_lr_schedule_table(float* out, int n, float lr, const FdLrSched* sched, hi
 int fd_step(int*, uint32_t*, hipStream_t) { ++hc::calls; return 0; }
 int fd_scale_cast(float*, void*, long long, float, hipStream_t) { ++hc::calls; return 0; }
 int fd_axpby(float*, const float*, const float*, float, float, long long, hipStream_t) { ++hc::calls; return 0; }
+// (the kernel's grid: ceil(n / 4 / 256) blocks, at most 4096 -- csrc/kernels/head_optim.hip grid_for)
+int fd_server_opt_grid(long long n) { return n > 0 ? (int)std::min<long long>((n / 4 + 255) / 256, 4096) : 0; }
+int fd_server_opt(float* master, float* x, float* m, float* v, void* shadow, long long n, int kind, float inv,
+                  float eta, float b1, float b2, float tau, float* stats, hipStream_t) {
+  ++hc::calls;
+  // the kernel walks n / 4 float4 of every stream it is given, and writes 2 floats per block of stats
+  if (n <= 0 || n % 4 != 0) hc::violations.push_back("server_opt: n % 4");
+  if (kind < 0 || kind > 3) hc::violations.push_back("server_opt: kind");
+  hc::span(master, n * 4, "server_opt master");
+  hc::span(x, n * 4, "server_opt x");
+  hc::span(m, n * 4, "server_opt m");
+  if (kind != 0) hc::span(v, n * 4, "server_opt v");
+  else if (v) hc::violations.push_back("server_opt: v with avgm");
+  hc::opt_span(shadow, n * 2, "server_opt shadow");
+  hc::opt_span(stats, 2LL * fd_server_opt_grid(n) * 4, "server_opt stats");
+  if (!std::isfinite(inv) || !(inv > 0.f) || !std::isfinite(eta) || !(eta > 0.f) || !std::isfinite(tau) ||
+      !(tau > 0.f) || !(b1 >= 0.f && b1 <= 1.f) || !(b2 >= 0.f && b2 <= 1.f))
+    hc::violations.push_back("server_opt: hyper-parameters out of range");
+  return 0;
+}
 }  // extern "C"
 
 // ------------------------------------------------------------------ driver
@@ -1146,6 +1166,49 @@ int main() {
     expect_reject("lr table lr NaN", [&] { lr_schedule_table(T_({4}, f32), std::nan(""), lin); });
     expect_reject("lr table empty", [&] { lr_schedule_table(T_({0}, f32), 2e-5, lin); });
     expect_reject("lr table no schedule", [&] { lr_schedule_table(T_({4}, f32), 2e-5, {}); });
+  }
+  // ---- FedOpt server step: four fp32 streams, the bf16 shadow, two stats floats per block
+  {
+    const int64_t n = 4096 * 1024 + 4 * 257;  // the grid-stride loop wraps, ragged last block
+    const int64_t nb = 2 * fd_server_opt_grid(n);
+    auto ms = T_({n}, f32), x = T_({n}, f32), m = T_({n}, f32), v = T_({n}, f32), sh = T_({n}, bf), st = T_({nb}, f32);
+    expect_ok("server_opt avgm", [&] { server_opt(ms, x, m, none, sh, 0, 0.5, 1.0, 0.9, 0.99, 1e-3, st); });
+    expect_ok("server_opt adagrad", [&] { server_opt(ms, x, m, v, sh, 1, 0.5, 1e-2, 0.9, 0.99, 1e-3, st); });
+    expect_ok("server_opt adam", [&] { server_opt(ms, x, m, v, sh, 2, 0.5, 1e-2, 0.9, 0.99, 1e-3, st); });
+    expect_ok("server_opt yogi, no shadow / stats", [&] { server_opt(ms, x, m, v, none, 3, 0.5, 1e-2, 0.9, 0.99, 1e-3,
+                                                                     none); });
+    auto s8 = T_({2048}, f32), x8 = T_({2048}, f32), m8 = T_({2048}, f32), st8 = T_({2 * 2}, f32);
+    expect_ok("server_opt small", [&] { server_opt(s8, x8, m8, none, none, 0, 0.5, 1.0, 0.0, 0.0, 1e-3, st8); });
+    auto xs = T_({n - 4}, f32), msh = T_({n - 4}, f32), vs = T_({n - 4}, f32), shs = T_({n - 4}, bf);
+    expect_reject("server_opt short x", [&] { server_opt(ms, xs, m, v, sh, 2, 0.5, 1e-2, 0.9, 0.99, 1e-3, st); });
+    expect_reject("server_opt short m", [&] { server_opt(ms, x, msh, v, sh, 2, 0.5, 1e-2, 0.9, 0.99, 1e-3, st); });
+    expect_reject("server_opt short v", [&] { server_opt(ms, x, m, vs, sh, 2, 0.5, 1e-2, 0.9, 0.99, 1e-3, st); });
+    expect_reject("server_opt short shadow", [&] { server_opt(ms, x, m, v, shs, 2, 0.5, 1e-2, 0.9, 0.99, 1e-3, st); });
+    expect_reject("server_opt adam without v", [&] { server_opt(ms, x, m, none, sh, 2, 0.5, 1e-2, 0.9, 0.99, 1e-3,
+                                                                st); });
+    expect_reject("server_opt avgm with v", [&] { server_opt(ms, x, m, v, sh, 0, 0.5, 1.0, 0.9, 0.99, 1e-3, st); });
+    expect_reject("server_opt kind", [&] { server_opt(ms, x, m, v, sh, 4, 0.5, 1e-2, 0.9, 0.99, 1e-3, st); });
+    auto xb = T_({n}, bf), shf = T_({n}, f32), sti = T_({nb}, i32);
+    expect_reject("server_opt x dtype", [&] { server_opt(ms, xb, m, v, sh, 2, 0.5, 1e-2, 0.9, 0.99, 1e-3, st); });
+    expect_reject("server_opt shadow dtype", [&] { server_opt(ms, x, m, v, shf, 2, 0.5, 1e-2, 0.9, 0.99, 1e-3, st); });
+    expect_reject("server_opt stats dtype", [&] { server_opt(ms, x, m, v, sh, 2, 0.5, 1e-2, 0.9, 0.99, 1e-3, sti); });
+    auto st_short = T_({nb - 1}, f32);
+    expect_reject("server_opt short stats", [&] { server_opt(ms, x, m, v, sh, 2, 0.5, 1e-2, 0.9, 0.99, 1e-3,
+                                                             st_short); });
+    auto s6 = T_({2046}, f32), x6 = T_({2046}, f32), m6 = T_({2046}, f32);
+    expect_reject("server_opt numel % 4", [&] { server_opt(s6, x6, m6, none, none, 0, 0.5, 1.0, 0.9, 0.99, 1e-3,
+                                                           none); });
+    auto xt = T_({2, n / 2}, f32).t();
+    expect_reject("server_opt non-contiguous x", [&] { server_opt(ms, xt, m, v, sh, 2, 0.5, 1e-2, 0.9, 0.99, 1e-3,
+                                                                  st); });
+    const double inf = HUGE_VAL;
+    expect_reject("server_opt eta NaN", [&] { server_opt(ms, x, m, v, sh, 2, 0.5, std::nan(""), 0.9, 0.99, 1e-3, st); });
+    expect_reject("server_opt eta inf", [&] { server_opt(ms, x, m, v, sh, 2, 0.5, inf, 0.9, 0.99, 1e-3, st); });
+    expect_reject("server_opt eta 0", [&] { server_opt(ms, x, m, v, sh, 2, 0.5, 0.0, 0.9, 0.99, 1e-3, st); });
+    expect_reject("server_opt tau 0", [&] { server_opt(ms, x, m, v, sh, 2, 0.5, 1e-2, 0.9, 0.99, 0.0, st); });
+    expect_reject("server_opt b1 = 1", [&] { server_opt(ms, x, m, v, sh, 2, 0.5, 1e-2, 1.0, 0.99, 1e-3, st); });
+    expect_reject("server_opt b2 < 0", [&] { server_opt(ms, x, m, v, sh, 2, 0.5, 1e-2, 0.9, -0.1, 1e-3, st); });
+    expect_reject("server_opt inv inf", [&] { server_opt(ms, x, m, v, sh, 2, inf, 1e-2, 0.9, 0.99, 1e-3, st); });
   }
   // ---- embedding backward (work = pieces + LayerNorm partials)
   {

@@ -290,6 +290,107 @@ __global__ __launch_bounds__(256) void axpby_kernel(float* dst, const float* x, 
 
 int grid_for(long long n4) { return (int)std::min<long long>((n4 + 255) / 256, 4096); }
 
+// FedOpt server step (Reddi et al., "Adaptive Federated Optimization"): FedAvg's finalisation with
+// a server optimizer in the same pass.  s = the all-reduced weighted sum (in master):
+//   avg = s * inv ; d = avg - x                                   (the pseudo-gradient)
+//   avgm    : m = b1 m + d                   ; x' = x + eta m
+//   adagrad : m = b1 m + (1 - b1) d ; v += d d
+//   adam    : m = b1 m + (1 - b1) d ; v = b2 v + (1 - b2) d d
+//   yogi    : m = b1 m + (1 - b1) d ; v -= (1 - b2) d d sign(v - d d)
+//   adaptive: x' = x + eta m / (sqrt(v) + tau)                    (no bias correction)
+// master = x = x', shadow = bf16(x').  Every product and sum is rounded on its own (contraction
+// off), 1 - b in fp32: the order of the fp32 torch chain in parallel/server_opt.py.  An alignment
+// pad (s = x = m = +0) stays +0 by arithmetic.
+enum { SOPT_AVGM = 0, SOPT_ADAGRAD = 1, SOPT_ADAM = 2, SOPT_YOGI = 3 };
+struct ServerOptArgs {
+  float* master;
+  float* x;
+  float* m;
+  float* v;        // null for avgm
+  bf16_t* shadow;  // nullable
+  float* stats;    // nullable: [2 * grid] per-block partials of sum d^2, sum (x' - x)^2
+  long long n4;
+  float inv, eta, b1, b2, tau;
+};
+
+template <int KIND>
+DEV void server_opt_elem(const ServerOptArgs& a, float s, float& x, float& m, float& v, float& sd, float& sx) {
+#pragma clang fp contract(off)
+  const float avg = s * a.inv;
+  const float d = avg - x;
+  float step;
+  if (KIND == SOPT_AVGM) {
+    m = m * a.b1;
+    m = m + d;
+    step = m * a.eta;
+  } else {
+    const float c1 = 1.f - a.b1, c2 = 1.f - a.b2;
+    const float t = d * c1;
+    m = m * a.b1;
+    m = m + t;
+    const float d2 = d * d;
+    if (KIND == SOPT_ADAGRAD) {
+      v = v + d2;
+    } else if (KIND == SOPT_ADAM) {
+      const float t2 = d2 * c2;
+      v = v * a.b2;
+      v = v + t2;
+    } else {
+      const float z = v - d2;
+      const float sg = (float)(z > 0.f) - (float)(z < 0.f);
+      float t2 = d2 * c2;
+      t2 = t2 * sg;
+      v = v - t2;
+    }
+    const float den = sqrtf(v) + a.tau;
+    step = m * a.eta;
+    step = step / den;
+  }
+  const float xn = x + step;
+  const float dx = xn - x;
+  sd = sd + d * d;
+  sx = sx + dx * dx;
+  x = xn;
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void server_opt_kernel(ServerOptArgs a) {
+  constexpr bool ADAPT = KIND != SOPT_AVGM;
+  float sd = 0.f, sx = 0.f;
+  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < a.n4; i += (long long)gridDim.x * 256) {
+    const float4 s4 = ld_nt(reinterpret_cast<const float4*>(a.master) + i);
+    const float4 x4 = ld_nt(reinterpret_cast<const float4*>(a.x) + i);
+    const float4 m4 = ld_nt(reinterpret_cast<const float4*>(a.m) + i);
+    float4 v4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (ADAPT) v4 = ld_nt(reinterpret_cast<const float4*>(a.v) + i);
+    const float ss[4] = {s4.x, s4.y, s4.z, s4.w};
+    float xx[4] = {x4.x, x4.y, x4.z, x4.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w}, vv[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) server_opt_elem<KIND>(a, ss[e], xx[e], mm[e], vv[e], sd, sx);
+    const float4 xo = make_float4(xx[0], xx[1], xx[2], xx[3]);
+    reinterpret_cast<float4*>(a.master)[i] = xo;
+    reinterpret_cast<float4*>(a.x)[i] = xo;
+    reinterpret_cast<float4*>(a.m)[i] = make_float4(mm[0], mm[1], mm[2], mm[3]);
+    if (ADAPT) reinterpret_cast<float4*>(a.v)[i] = make_float4(vv[0], vv[1], vv[2], vv[3]);
+    if (a.shadow) reinterpret_cast<uint2*>(a.shadow)[i] = make_uint2(pack_bf2(xo.x, xo.y), pack_bf2(xo.z, xo.w));
+  }
+  if (!a.stats) return;  // uniform over the launch
+  // lanes -> wave (shuffles) -> block (LDS, fixed order) -> one plain store per block: no atomics,
+  // so the partials are the same bits every run
+  __shared__ float red[2][4];
+  sd = wave_sum(sd);
+  sx = wave_sum(sx);
+  if ((threadIdx.x & 63) == 0) {
+    red[0][threadIdx.x >> 6] = sd;
+    red[1][threadIdx.x >> 6] = sx;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    const float* r = red[threadIdx.x];
+    a.stats[2 * blockIdx.x + threadIdx.x] = ((r[0] + r[1]) + r[2]) + r[3];
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -417,6 +518,28 @@ int fd_step(int* step, uint32_t* seed, hipStream_t st) {
 int fd_scale_cast(float* p, void* shadow, long long n, float scale, hipStream_t st) {
   if (n % 4 != 0) return 1;
   hipLaunchKernelGGL(scale_cast_kernel, dim3(grid_for(n / 4)), dim3(256), 0, st, p, (bf16_t*)shadow, n / 4, scale);
+  return 0;
+}
+
+// Blocks of an fd_server_opt launch over n floats (its stats buffer holds 2 floats per block).
+int fd_server_opt_grid(long long n) { return n > 0 ? grid_for(n / 4) : 0; }
+
+// The FedOpt server step over n floats (server_opt_kernel).  kind: 0 avgm (v == nullptr: no v
+// traffic), 1 adagrad, 2 adam, 3 yogi.  stats (nullable): 2 * fd_server_opt_grid(n) floats.
+int fd_server_opt(float* master, float* x, float* m, float* v, void* shadow, long long n, int kind, float inv,
+                  float eta, float b1, float b2, float tau, float* stats, hipStream_t st) {
+  if (n <= 0 || n % 4 != 0) return 1;
+  if (!master || !x || !m) return 2;
+  if (kind < SOPT_AVGM || kind > SOPT_YOGI) return 3;
+  if ((kind != SOPT_AVGM) != (v != nullptr)) return 4;
+  const ServerOptArgs a{master, x, m, v, (bf16_t*)shadow, stats, n / 4, inv, eta, b1, b2, tau};
+  const dim3 grid(grid_for(n / 4)), block(256);
+  switch (kind) {
+    case SOPT_AVGM: hipLaunchKernelGGL(server_opt_kernel<SOPT_AVGM>, grid, block, 0, st, a); break;
+    case SOPT_ADAGRAD: hipLaunchKernelGGL(server_opt_kernel<SOPT_ADAGRAD>, grid, block, 0, st, a); break;
+    case SOPT_ADAM: hipLaunchKernelGGL(server_opt_kernel<SOPT_ADAM>, grid, block, 0, st, a); break;
+    default: hipLaunchKernelGGL(server_opt_kernel<SOPT_YOGI>, grid, block, 0, st, a); break;
+  }
   return 0;
 }
 

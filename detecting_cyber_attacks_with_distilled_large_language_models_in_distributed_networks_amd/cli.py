@@ -146,6 +146,7 @@ def _virtual(argv):
         report["rounds"].append({
             "round": r, "fedavg_ms": h["fedavg_ms"], "aggregated_confusion": h["aggregated_confusion"],
             "aggregated_accuracy": 100.0 * (tp + tn) / max(tp + tn + fp + fn, 1),
+            **({k: h[k] for k in ("delta_l2", "step_l2") if k in h}),  # (a server optimizer's step)
             "clients": [{"client": c["client"], "local_test": c["local_test"], "aggregated_test": c["aggregated_test"],
                          "epoch_losses": c["train"]["epoch_losses"], "train_steps": c["train"]["steps"],
                          "rel_l2_local_to_aggregate": c["rel_l2_local_to_aggregate"],
@@ -153,7 +154,7 @@ def _virtual(argv):
                          **({"teacher_test": c["teacher_test"]} if "teacher_test" in c else {})}
                         for c in h["clients"]]})
     if cfg.save_checkpoints:
-        ck.save_global(client.model, cfg.out_dir, cfg.rounds)
+        ck.save_global(client.model, cfg.out_dir, cfg.rounds, server=client.server)
     path = os.path.join(cfg.out_dir, "virtual_report.json")
     with open(path, "w") as f:
         json.dump(report, f, indent=1)

@@ -64,6 +64,13 @@ class FedConfig:
     gpus_per_client: int = 1                # >1: each client is k data-parallel GPUs (parallel/dp.py)
     dp_graph: bool = False                  # capture data-parallel steps (collectives) in the HIP graph
     weighted_fedavg: bool = False           # reference is unweighted (server.py:73-76)
+    # FedOpt server optimizer (parallel/server_opt.py; Reddi et al., "Adaptive Federated Optimization"):
+    # avg - w_global is a pseudo-gradient for a server-side momentum / Adagrad / Adam / Yogi step.
+    # "fedavg": the plain mean (reference).  server_lr 1.0 suits "avgm"; the adaptive kinds want ~1e-2
+    server_opt: str = "fedavg"              # "fedavg" | "avgm" | "adagrad" | "adam" | "yogi"
+    server_lr: float = 1.0
+    server_betas: tuple = (0.9, 0.99)
+    server_tau: float = 1e-3                # adaptivity floor: v starts at tau^2
     participation: float = 1.0              # fraction of clients aggregated per round
     timeout_s: float = 300.0                # server.py:10 / client1.py:22
     heartbeat_s: float = 1.0                # failure detection (parallel/health.py); 0 disables

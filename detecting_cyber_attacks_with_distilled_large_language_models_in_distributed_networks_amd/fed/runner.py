@@ -30,6 +30,7 @@ from ..models import DDoSClassifier, DistilBertConfig
 from ..parallel import comm, health
 from ..parallel.dp import DPShardLoader, GradSync, dp_seed_offset, make_topology
 from ..parallel.fedavg import broadcast_model, fedavg_
+from ..parallel.server_opt import check_server_config, make_server_optimizer
 from ..utils import checkpoint as ck
 from ..utils import faults
 from ..utils.logging import TagLogger
@@ -105,6 +106,7 @@ class FederatedClient:
     # ------------------------------------------------------------------ setup
     def setup(self):
         cfg, log = self.cfg, self.log
+        check_server_config(cfg)  # (an unknown kind, a bad value, or transport=tcp: refused before any work)
         log.phase("Starting client")
         with self.timer("preprocess"):
             if self.frame is None:
@@ -166,6 +168,15 @@ class FederatedClient:
         self.history: List[Dict] = []
         if cfg.resume:
             self._resume()
+        # FedOpt server optimizer (parallel/server_opt.py; None: plain FedAvg).  Built with the round's
+        # starting weights loaded -- the broadcast init or the aggregate a resumed job loads -- which
+        # become its x; a resumed job then restores the moments that go with that aggregate.
+        self.server = make_server_optimizer(self.model, cfg, log=log)
+        if self.server is not None:
+            log.info(f"server optimizer: {self.server.kind} (lr {self.server.lr:g}, betas "
+                     f"({self.server.b1:g}, {self.server.b2:g}), tau {self.server.tau:g})")
+            if self.start_round > 0:
+                self._resume_server()
         self.health = None
         if self.di.distributed and cfg.heartbeat_s > 0 and cfg.transport != "tcp":
             self.health = health.start(cfg.heartbeat_s, cfg.heartbeat_stale_s, cfg.timeout_s)
@@ -224,6 +235,35 @@ class FederatedClient:
             path = ck.client_ckpt_path(cfg.out_dir, self.client_id)
             if ck.load_model(self.model, path):
                 log.info(f"loading pre-trained model from {path}")
+
+    def _resume_server(self):
+        """The server optimizer's moments of the aggregate ``_resume`` loaded: rank 0 reads
+        ``ddos_distilbert_server_opt.pth`` and broadcasts m / v (through the native communicator when
+        it is configured).  A missing file or one of another kind fails the job on every rank -- rank
+        0's verdict is broadcast first, so no rank is left waiting in a collective."""
+        import torch.distributed as dist
+        cfg, server = self.cfg, self.server
+        err = ""
+        if self.di.is_main or not self.di.distributed:
+            try:
+                ck.load_server_opt(server, cfg.out_dir)
+            except RuntimeError as e:
+                err = str(e)
+        if self.di.distributed:
+            if comm.broadcast_float(1.0 if err else 0.0, src=0) != 0.0:
+                raise RuntimeError(err or "rank 0 could not restore the server optimizer state (see its log)")
+            server.rounds = int(comm.broadcast_float(float(server.rounds), src=0))
+            for t in (server.m, server.v):
+                if t is None:
+                    continue
+                if self.comm is not None:
+                    self.comm.broadcast_(t, root=0)
+                else:
+                    dist.broadcast(t, src=0)
+        elif err:
+            raise RuntimeError(err)
+        self.log.info(f"server optimizer state restored from {ck.server_opt_path(cfg.out_dir)} "
+                      f"({server.rounds} step(s) so far)")
 
     # ------------------------------------------------------------------ one round
     def run_round(self, r: int) -> Dict:
@@ -287,14 +327,19 @@ class FederatedClient:
                 if self.topo.dp:
                     total_w = self._dp_share_model(total_w)
             else:
-                total_w = fedavg_(model, weight=weight, participate=contributes, comm=self.comm)
+                total_w = fedavg_(model, weight=weight, participate=contributes, comm=self.comm, server=self.server)
             if model.device.type == "cuda":
                 torch.cuda.synchronize()
             t_fed = time.perf_counter() - t0
         log.info(f"updated with aggregated model (participated={contributes}, total weight={total_w:g}, "
                  f"{t_fed * 1e3:.2f} ms)")
+        norms = self.server.last if self.server is not None and total_w > 0 else None
+        if norms is not None:
+            log.info(f"server {self.server.kind} step: |avg - global| = {norms['delta_l2']:.6g}, "
+                     f"|step| = {norms['step_l2']:.6g}")
         if self.di.is_main and cfg.save_checkpoints:
-            ck.save_global(model, cfg.out_dir, r + 1)  # weights, then the round tag (_resume)
+            # weights, the server optimizer's moments, then the round tag (_resume)
+            ck.save_global(model, cfg.out_dir, r + 1, server=self.server)
         faults.maybe_kill(self.idx, r, cfg.out_dir, self.topo.dp_rank, phase="post_fedavg")
         log.info("evaluating aggregated model on validation set...")
         with self.timer("eval"):
@@ -316,6 +361,8 @@ class FederatedClient:
                "aggregated_val": _metrics_record(val_agg), "aggregated_test": _metrics_record(agg)}
         if teacher_test is not None:
             rec["teacher_test"] = teacher_test
+        if norms is not None:
+            rec.update(delta_l2=norms["delta_l2"], step_l2=norms["step_l2"])
         self.history.append(rec)
         if self.writer:
             ck.save_fed_state(cfg.out_dir, self.client_id, {"completed_rounds": r + 1, "history": self.history})
@@ -386,14 +433,17 @@ class FederatedClient:
 
 
 @torch.no_grad()
-def _average_masters(model, states: List[torch.Tensor]) -> None:
+def _average_masters(model, states: List[torch.Tensor], server=None) -> Optional[Dict]:
     """``fedavg_``'s arithmetic in one process: the SUM of the clients' fp32 masters (what the
     all-reduce computes; for two clients a + b is exact in any order), then the fused 1/N scale +
-    bf16 shadow refresh (``scale_cast``) on GPU."""
+    bf16 shadow refresh (``scale_cast``) on GPU -- or, with a server optimizer, its step on that sum
+    (``ServerOptimizer.apply_``, whose norms are returned)."""
     A = model.arena
     A.master.copy_(states[0])
     for s in states[1:]:
         A.master.add_(s)
+    if server is not None:
+        return server.apply_(model, float(len(states)))
     if A.master.is_cuda:
         from ..ops import kernels as K
         K.scale_cast(A.master, A.shadow, 1.0 / len(states))
@@ -425,6 +475,8 @@ def warm_start(client: "FederatedClient", epochs: int = 1, rows: int = 225_745, 
     with torch.no_grad():
         model.rng.zero_()
     model.torch_counter = 0
+    if getattr(client, "server", None) is not None:
+        client.server.reset(model)  # the server optimizer starts from the warm weights, moments cleared
     return {"train": tr, "public_test": test, "rows": rows, "seed": seed, "profile": profile,
             "train_rows": len(data.train)}
 
@@ -455,6 +507,11 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
     the R-round virtual run equals the N-rank collective ``run_federated`` run bit for bit
     (tests/test_virtual_rounds.py, N = 2, R = 2 on gloo).
 
+    With a server optimizer (``cfg.server_opt``, parallel/server_opt.py) the job's ``client.server`` --
+    the object ``run_round`` hands to ``fedavg_`` -- makes its step on the same sum instead of the 1/N
+    scale, and each round's record carries its ``delta_l2`` / ``step_l2``
+    (tests/test_server_opt_cpu.py: equal to the 2-rank gloo run bit for bit).
+
     Returns ``rounds`` (one record per round: per-client local / aggregated metrics, the pooled
     aggregated confusion, the FedAvg time) plus the LAST round's ``clients`` /
     ``aggregated_confusion`` / ``fedavg_ms`` at the top level (the 1-round API of earlier rounds).
@@ -471,6 +528,13 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
     dev = model.device
     A = model.arena
     glob = A.master.detach().clone()  # what every client starts the round from
+    # the job's FedOpt server optimizer (None: plain FedAvg) -- the object run_round hands to fedavg_
+    server = getattr(client, "server", None)
+    if server is not None and not torch.equal(server.x, glob):
+        # the weights were replaced after setup() (a checkpoint loaded by hand): the server's x is the
+        # global model by definition, and moments of other weights mean nothing
+        client.log.info("[WARN] the model changed since the server optimizer was built: server state reset")
+        server.reset(model)
     t_init = teacher.arena.master.detach().clone() if teacher is not None else None
     say = progress or (lambda msg: None)
     # per-client state that survives the rounds (a real client's process keeps it)
@@ -532,7 +596,11 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
             say(f"round {r + 1}/{rounds} client {v + 1}/{n_clients}: local acc {local['accuracy']:.3f} % "
                 f"f1 {local['f1']:.5f} ({tr['steps']} steps, {time.perf_counter() - t0:.1f} s)")
         t0 = time.perf_counter()
-        _average_masters(model, locals_)
+        norms = None
+        if server is None:
+            _average_masters(model, locals_)
+        else:
+            norms = _average_masters(model, locals_, server)
         if dev.type == "cuda":
             torch.cuda.synchronize()
         fed_ms = 1e3 * (time.perf_counter() - t0)
@@ -546,6 +614,8 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
         pooled = _pooled(recs, "aggregated_test")
         hist.append({"round": r + 1, "clients": recs, "fedavg_ms": fed_ms, "aggregated_confusion": pooled,
                      "local_confusion": _pooled(recs, "local_test")})
+        if norms is not None:  # the server step: how far the average drifted, how far the server moved
+            hist[-1].update(delta_l2=norms["delta_l2"], step_l2=norms["step_l2"])
         (tn, fp), (fn, tp) = pooled
         say(f"round {r + 1}/{rounds} aggregate: pooled acc {100.0 * (tp + tn) / max(tp + tn + fp + fn, 1):.3f} %")
     last = hist[-1]

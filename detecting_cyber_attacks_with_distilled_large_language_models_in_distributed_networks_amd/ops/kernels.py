@@ -1129,3 +1129,21 @@ def scale_cast(p, shadow=None, scale=1.0):
 
 def axpby(dst, x, y=None, a=1.0, b=0.0):
     ext().axpby(dst, x, y, a, b)
+
+
+SERVER_OPT_KINDS = {"avgm": 0, "adagrad": 1, "adam": 2, "yogi": 3}
+
+
+def server_opt_grid(n):
+    """Blocks of a ``server_opt`` launch over ``n`` floats (its ``stats`` holds two floats per block)."""
+    return int(ext().server_opt_grid(int(n)))
+
+
+def server_opt(master, x, m, v, shadow, kind, inv, eta, b1, b2, tau, stats=None):
+    """The FedOpt server step in one pass (head_optim.hip ``server_opt_kernel``): ``master`` holds the
+    all-reduced weighted sum, ``inv`` = 1 / total weight; on return master = x = x', m / v advanced,
+    shadow = bf16(x').  ``kind``: "avgm" (v is None) | "adagrad" | "adam" | "yogi".  ``stats``
+    (fp32, >= 2 * ``server_opt_grid(n)``): per-block partial sums of d^2 and (x' - x)^2, [block][2]."""
+    if kind not in SERVER_OPT_KINDS:
+        raise ValueError(f"server_opt: unknown kind {kind!r} (one of {sorted(SERVER_OPT_KINDS)})")
+    ext().server_opt(master, x, m, v, shadow, SERVER_OPT_KINDS[kind], inv, eta, b1, b2, tau, stats)

@@ -11,7 +11,9 @@ followed by one fused HIP pass that applies the 1/N (or 1/sum-of-weights)
 scale and re-casts the bf16 compute shadow.  Options the reference lacks:
 sample-count weighting (pre-scale by n_k) and partial participation (a
 non-participating / dropped client contributes weight 0 and receives the
-average of the live clients).
+average of the live clients), and FedOpt server optimizers (``fedavg_(..., server=)``,
+parallel/server_opt.py: the same all-reduce, then one fused server step on the sum instead of the
+scale).
 
 ``aggregate_state_dicts`` keeps the reference's server-side API for
 state_dict lists (floating tensors only -- an int64 buffer would make the
@@ -46,14 +48,20 @@ def broadcast_model(model, src: int = 0, comm=None):
 
 
 @torch.no_grad()
-def fedavg_(model, weight: float = 1.0, participate: bool = True, comm=None) -> float:
+def fedavg_(model, weight: float = 1.0, participate: bool = True, comm=None, server=None) -> float:
     """In-place FedAvg of ``model`` across all ranks; returns the total weight.
 
     weight:      this client's aggregation weight (1 = unweighted, n_k = sample-weighted)
     participate: False -> this client's update is dropped this round (fault injection /
                  partial participation); it still receives the aggregate.
     comm:        optional ``parallel.rccl.NativeComm``; default is the torch.distributed group.
+    server:      optional ``parallel.server_opt.ServerOptimizer``: the pre-scale and the all-reduce are
+                 the same, and its step on the weighted sum replaces the final 1/W scale (every rank
+                 holds the same server state, so the ranks stay identical; a client that does not
+                 participate still makes the step).  Its norms are left in ``server.last``.
     """
+    if server is not None:
+        return _fedopt_(model, weight, participate, comm, server)
     A = model.arena
     w = float(weight) if participate else 0.0
     if not _dist_on():
@@ -88,6 +96,42 @@ def fedavg_(model, weight: float = 1.0, participate: bool = True, comm=None) -> 
         dist.all_reduce(A.master, op=dist.ReduceOp.SUM)
         A.master.mul_(1.0 / total)
         model.sync_shadow(force=True)
+    return total
+
+
+@torch.no_grad()
+def _fedopt_(model, weight: float, participate: bool, comm, server) -> float:
+    """``fedavg_`` with a server optimizer: the same weight exchange, pre-scale and all-reduce, then
+    ``server.apply_`` on the weighted sum instead of the 1/W scale."""
+    A = model.arena
+    w = float(weight) if participate else 0.0
+    if not _dist_on():
+        if w == 0.0:
+            return 0.0
+        server.apply_(model, 1.0)  # one client: its weights are the mean
+        return w
+    dev = A.master.device
+    wt = torch.tensor([w], dtype=torch.float64, device=dev)
+    use_native = comm is not None and A.master.is_cuda
+
+    def allreduce(t):
+        if use_native:
+            comm.all_reduce_(t, "sum")
+        else:
+            dist.all_reduce(t, op=dist.ReduceOp.SUM)
+
+    allreduce(wt)
+    total = float(wt.item())
+    if total <= 0:
+        raise RuntimeError("FedAvg round with no participating clients")
+    if w != 1.0:
+        if A.master.is_cuda:
+            from ..ops import kernels as K
+            K.scale_cast(A.master, None, w)          # pre-scale (0 drops the update)
+        else:
+            A.master.mul_(w)
+    allreduce(A.master)
+    server.apply_(model, total)  # fused server step + bf16 shadow refresh on GPU
     return total
 
 

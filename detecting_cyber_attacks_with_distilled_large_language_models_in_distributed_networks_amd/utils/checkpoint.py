@@ -59,15 +59,38 @@ def global_tag_path(out_dir: str) -> str:
     return os.path.join(out_dir, "ddos_distilbert_model.json")
 
 
-def save_global(model, out_dir: str, round_done: int) -> str:
+def server_opt_path(out_dir: str) -> str:
+    return os.path.join(out_dir, "ddos_distilbert_server_opt.pth")
+
+
+def save_global(model, out_dir: str, round_done: int, server=None) -> str:
     """Rank 0: the round-``round_done`` aggregate, then its round tag (written after the
-    weights, so a tag never names a checkpoint that is not on disk yet)."""
+    weights, so a tag never names a checkpoint that is not on disk yet).  With a server optimizer
+    (parallel/server_opt.py) its state goes in between: a tag also never names server moments that
+    are not on disk.  The aggregate's own file keeps its 102 keys."""
     path = save_model(model, global_ckpt_path(out_dir))
+    if server is not None:
+        _atomic_save(server.state_dict(), server_opt_path(out_dir))
     tag = global_tag_path(out_dir)
     with open(tag + ".tmp", "w") as f:
         json.dump({"round": int(round_done)}, f)
     os.replace(tag + ".tmp", tag)
     return path
+
+
+def load_server_opt(server, out_dir: str) -> None:
+    """Rank 0, resuming at a round > 0 with a server optimizer: its moments from
+    ``ddos_distilbert_server_opt.pth``.  A missing file, or one of another kind / size, is an error --
+    restarting the moments silently would change the run."""
+    path = server_opt_path(out_dir)
+    if not os.path.exists(path):
+        raise RuntimeError(f"resuming a run with server_opt={server.kind!r}, but {path} is missing: the server "
+                           f"moments cannot be restored (use resume=False or a fresh out_dir to start over)")
+    sd = torch.load(path, map_location="cpu", weights_only=True)
+    try:
+        server.load_state_dict(sd)
+    except ValueError as e:
+        raise RuntimeError(f"{path}: {e}") from None
 
 
 def load_global_round(out_dir: str) -> int:
