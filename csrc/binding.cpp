@@ -42,8 +42,8 @@ int fd_gemm_dw2(const void* A0, const void* B0, float* C0, int M0, int N0, const
                 int M1, int N1, int K, float* workspace, long long workspace_elems, int accumulate,
                 const FdAdamEpi* adams, int defer, int* splits_out, hipStream_t st);
 int fd_gemm_dw2_splits(int M0, int N0, int M1, int N1, int K);
-int fd_gemm_dw_batch(int n, const FdDwProb* probs, int K, const int* step, const float* hyper, int cfg,
-                     const FdAdamRest* rest, const FdLrSched* sched, float prox_mu, hipStream_t st);
+int fd_gemm_dw_batch(int n, const FdDwProb* probs, int K, const int* step, const FdAdamHyper* h, int cfg,
+                     const FdAdamRest* rest, hipStream_t st);
 int fd_gemm_ln_set_diag(int diag);
 int fd_gemm_dwb_set_mix(int mode);
 long long fd_gemm_dwb_mixed_launches();
@@ -132,18 +132,16 @@ int fd_head_ln_bwd(const void* hidden, int B, int T, int D, const float* W, cons
                    uint32_t site, uint32_t thr, float dscale, const int* row_map, int* nblk_out, hipStream_t st);
 int fd_eval_metrics(const float* logits, const long long* labels, int B, double* acc, long long* counts,
                     float* prob1, long long* preds, hipStream_t st);
-int fd_adam(float* p, const float* g, float* m, float* v, void* shadow, long long n, const int* step, float lr,
-            float b1, float b2, float eps, float wd, int decoupled, const unsigned char* touched,
-            const unsigned char* now, long long skip_off, long long skip_rows, int row_len, const long long* runs,
-            int nruns, long long run_total4, const float* run_wd, const FdLrSched* sched, float prox_mu,
-            const float* anchor, hipStream_t st);
+int fd_adam(float* p, const float* g, float* m, float* v, void* shadow, long long n, const int* step,
+            const FdAdamHyper* h, const unsigned char* touched, const unsigned char* now, long long skip_off,
+            long long skip_rows, int row_len, const long long* runs, int nruns, long long run_total4,
+            const float* run_wd, const float* anchor, hipStream_t st);
 int fd_adam_rows(float* p, const float* g, float* m, float* v, void* shadow, int rows, int row_len, const int* step,
-                 float lr, float b1, float b2, float eps, const unsigned char* ever, const unsigned char* now,
-                 float wd, int decoupled, const FdLrSched* sched, float prox_mu, const float* anchor,
+                 const FdAdamHyper* h, const unsigned char* ever, const unsigned char* now, const float* anchor,
                  hipStream_t st);
 int fd_adam_lazy_decay(float* p, void* shadow, int* done, const unsigned char* ever, int rows, int row_len,
-                       const int* step, int adj, float lr, float wd, const void* ids, int ids64, long long n,
-                       const FdLrSched* sched, hipStream_t st);
+                       const int* step, int adj, const FdAdamHyper* h, const void* ids, int ids64, long long n,
+                       hipStream_t st);
 int fd_lr_schedule_table(float* out, int n, float lr, const FdLrSched* sched, hipStream_t st);
 int fd_step(int* step, uint32_t* seed, hipStream_t st);
 int fd_scale_cast(float* p, void* shadow, long long n, float scale, hipStream_t st);
@@ -276,13 +274,41 @@ int64_t gemm_colsum(int64_t epi, const at::Tensor& A, const at::Tensor& B, const
   return blocks;
 }
 
+// A learning-rate schedule argument: empty (constant) or [kind, warmup, total, offset] (adam_epi.h FdLrSched).
+FdLrSched need_sched(const std::vector<int64_t>& sched, const char* what) {
+  if (sched.empty()) return FdLrSched{};
+  TORCH_CHECK(sched.size() == 4, what, ": sched is [kind, warmup, total, offset], got ", sched.size(), " entries");
+  auto i32 = [](int64_t x) { return x < 0 ? -1 : x > (1 << 30) ? 1 << 30 : (int)x; };  // (outside int32: refused too)
+  const FdLrSched s{i32(sched[0]), i32(sched[1]), i32(sched[2]), i32(sched[3])};
+  TORCH_CHECK(fd_lr_sched_rc(&s) == 0, what, ": sched ", at::IntArrayRef(sched), ": kind must be 0 (constant), 1 "
+              "(linear) or 2 (constant with warmup); warmup, total and offset >= 0 and < 2^30; warmup <= total for "
+              "the linear schedule");
+  return s;
+}
+
+// What Python passes -> the descriptor every Adam launcher takes, refused by the launchers' own rules.
+FdAdamHyper need_hyper(double lr, double b1, double b2, double eps, double wd, bool decoupled,
+                       const std::vector<int64_t>& sched, double mu, const char* what) {
+  const FdAdamHyper h{(float)lr, (float)b1, (float)b2, (float)eps, (float)wd, decoupled ? 1 : 0,
+                      need_sched(sched, what), (float)mu};
+  const int rc = fd_adam_hyper_rc(&h);
+  TORCH_CHECK(rc != 11, what, ": lr must be finite");
+  TORCH_CHECK(rc != 12, what, ": weight decay must be finite and >= 0");
+  TORCH_CHECK(rc == 0, what, ": prox_mu must be finite and >= 0, got ", mu);  // (the schedule: need_sched)
+  return h;
+}
+// ... from a fused launch's hp = [lr, b1, b2, eps, wd, decoupled]
+FdAdamHyper need_hyper(const std::vector<double>& hp, const std::vector<int64_t>& sched, double mu, const char* what) {
+  TORCH_CHECK(hp.size() == 6, "fused adam: hyper-parameters [lr, b1, b2, eps, wd, decoupled]");
+  return need_hyper(hp[0], hp[1], hp[2], hp[3], hp[4], hp[5] != 0.0, sched, mu, what);
+}
+
 // Adam descriptors for fused weight-gradient epilogues.  st = [p, m, v, shadow] per problem
-// + the device step counter last; hp = [lr, b1, b2, eps, wd, decoupled].  Each state tensor
+// + the device step counter last; h: the step's hyper-parameters (need_hyper).  Each state tensor
 // must be laid out exactly like the gradient it replaces (same numel, contiguous).
-void adam_descs(const std::vector<at::Tensor>& st, const std::vector<double>& hp, const at::Tensor* const* grads,
+void adam_descs(const std::vector<at::Tensor>& st, const FdAdamHyper& h, const at::Tensor* const* grads,
                 int nprob, FdAdamEpi* out) {
   TORCH_CHECK((int)st.size() == 4 * nprob + 1, "fused adam: expected ", 4 * nprob + 1, " state tensors");
-  TORCH_CHECK(hp.size() == 6, "fused adam: hyper-parameters [lr, b1, b2, eps, wd, decoupled]");
   const at::Tensor& step = st.back();
   need(step, at::kInt, "adam step");
   for (int i = 0; i < nprob; ++i) {
@@ -302,8 +328,8 @@ void adam_descs(const std::vector<at::Tensor>& st, const std::vector<double>& hp
     a.v = st[4 * i + 2].data_ptr<float>();
     a.sh = (sh.defined() && sh.numel() > 0) ? reinterpret_cast<uint16_t*>(sh.data_ptr()) : nullptr;
     a.step = step.data_ptr<int>();
-    a.lr = (float)hp[0]; a.b1 = (float)hp[1]; a.b2 = (float)hp[2]; a.eps = (float)hp[3]; a.wd = (float)hp[4];
-    a.decoupled = hp[5] != 0.0 ? 1 : 0;
+    a.lr = h.lr; a.b1 = h.b1; a.b2 = h.b2; a.eps = h.eps; a.wd = h.wd;
+    a.decoupled = h.decoupled;
   }
 }
 
@@ -321,7 +347,7 @@ void gemm_dw(const at::Tensor& A, const at::Tensor& B, const at::Tensor& C, cons
   TORCH_CHECK(K % 64 == 0 && M % 128 == 0 && N % 64 == 0, "gemm_dw: K % 64, M % 128, N % 64 required");
   FdAdamEpi ad{};
   const at::Tensor* gs[1] = {&C};
-  if (!adam.empty()) adam_descs(adam, hp, gs, 1, &ad);
+  if (!adam.empty()) adam_descs(adam, need_hyper(hp, {}, 0.0, "gemm_dw"), gs, 1, &ad);
   check_rc(fd_gemm(2, 5, A.data_ptr(), B.data_ptr(), C.data_ptr(), (int)M, (int)N, (int)K, (int)M, (int)N, (int)N,
                    nullptr, nullptr, 0, nullptr, 0, workspace.data_ptr<float>(), workspace.numel(),
                    accumulate ? 1 : 0, adam.empty() ? nullptr : &ad, nullptr, nullptr, stream()),
@@ -348,7 +374,7 @@ int64_t gemm_dw2(const at::Tensor& A0, const at::Tensor& B0, const at::Tensor& C
   TORCH_CHECK(K % 64 == 0, "gemm_dw2: K must be a multiple of 64");
   need(workspace, at::kFloat, "workspace");
   FdAdamEpi ad[2]{};
-  if (!adam.empty()) adam_descs(adam, hp, Cs, 2, ad);
+  if (!adam.empty()) adam_descs(adam, need_hyper(hp, {}, 0.0, "gemm_dw2"), Cs, 2, ad);
   int splits = 0;
   check_rc(fd_gemm_dw2(A0.data_ptr(), B0.data_ptr(), C0.data_ptr<float>(), (int)A0.size(1), (int)B0.size(1),
                        A1.data_ptr(), B1.data_ptr(), C1.data_ptr<float>(), (int)A1.size(1), (int)B1.size(1), (int)K,
@@ -364,34 +390,9 @@ void need_decays(const std::vector<double>& wd, size_t n, const char* what) {
   for (double w : wd) TORCH_CHECK(std::isfinite(w) && w >= 0.0, what, ": a weight decay must be finite and >= 0");
 }
 
-// A learning-rate schedule argument: empty (constant) or [kind, warmup, total, offset] (FdLrSched,
-// adam_epi.h; the launch's lr is its base rate).
-FdLrSched need_sched(const std::vector<int64_t>& sched, double lr, const char* what) {
-  TORCH_CHECK(std::isfinite(lr), what, ": lr must be finite");
-  FdLrSched s{};
-  if (sched.empty()) return s;
-  TORCH_CHECK(sched.size() == 4, what, ": sched is [kind, warmup, total, offset], got ", sched.size(), " entries");
-  const int64_t lim = int64_t(1) << 30;  // (offset + step and total - warmup stay inside int32)
-  TORCH_CHECK(sched[0] >= 0 && sched[0] <= 2, what, ": sched kind must be 0 (constant), 1 (linear) or 2 "
-              "(constant with warmup), got ", sched[0]);
-  TORCH_CHECK(sched[1] >= 0 && sched[1] < lim, what, ": sched warmup must be >= 0 and < 2^30, got ", sched[1]);
-  TORCH_CHECK(sched[2] >= 0 && sched[2] < lim, what, ": sched total must be >= 0 and < 2^30, got ", sched[2]);
-  TORCH_CHECK(sched[3] >= 0 && sched[3] < lim, what, ": sched offset must be >= 0 and < 2^30, got ", sched[3]);
-  TORCH_CHECK(sched[0] != 1 || sched[1] <= sched[2], what, ": sched warmup (", sched[1], ") must be <= total (",
-              sched[2], ") for the linear schedule");
-  s.kind = (int)sched[0]; s.warmup = (int)sched[1]; s.total = (int)sched[2]; s.offset = (int)sched[3];
-  return s;
-}
-
-// A FedProx proximal coefficient (adam_common.h adam_elem): finite and non-negative.
-void need_mu(double mu, const char* what) {
-  TORCH_CHECK(std::isfinite(mu) && mu >= 0.0, what, ": prox_mu must be finite and >= 0, got ", mu);
-}
-
 // The anchor that goes with state `p` (laid out like it: fp32, contiguous, the same device and
-// element count), or nullptr when none is given -- which only mu == 0 allows.
+// element count), or nullptr when none is given -- which only mu == 0 (need_hyper's) allows.
 const float* need_anchor(double mu, const c10::optional<at::Tensor>& anchor, const at::Tensor& p, const char* what) {
-  need_mu(mu, what);
   if (!(anchor.has_value() && anchor->defined())) {
     TORCH_CHECK(mu == 0.0, what, ": prox_mu != 0 needs an anchor");
     return nullptr;
@@ -465,17 +466,16 @@ void gemm_dw_batch(const std::vector<at::Tensor>& As, const std::vector<at::Tens
     pr[i].bias = biases[i].data_ptr<float>();
   }
   TORCH_CHECK(!adam.empty() || sched.empty(), "gemm_dw_batch: sched needs the fused Adam");
-  need_mu(prox_mu, "gemm_dw_batch");
   TORCH_CHECK(!adam.empty() || (prox_mu == 0.0 && anchor.empty()), "gemm_dw_batch: a proximal term needs the fused Adam");
   TORCH_CHECK(prox_mu == 0.0 || !anchor.empty(), "gemm_dw_batch: prox_mu != 0 needs the anchors");
   TORCH_CHECK(anchor.empty() || anchor.size() == n + (rest.empty() ? 0 : 1),
               "gemm_dw_batch: one anchor per problem, and the arena's with the rest of the step; got ", anchor.size());
-  const FdLrSched sc = need_sched(sched, adam.empty() || hp.empty() ? 0.0 : hp[0], "gemm_dw_batch");
   std::vector<FdAdamEpi> ad(n);
   const int* step = nullptr;
-  float hyper[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  FdAdamHyper hy{};  // (hp[0] is the base rate of sched)
   if (!adam.empty()) {
-    adam_descs(adam, hp, cs.data(), (int)n, ad.data());
+    hy = need_hyper(hp, sched, prox_mu, "gemm_dw_batch");
+    adam_descs(adam, hy, cs.data(), (int)n, ad.data());
     for (size_t i = 0; i < n; ++i) {
       TORCH_CHECK(!accumulate[i], "gemm_dw_batch: a fused Adam step cannot accumulate into a gradient");
       pr[i].p = ad[i].p; pr[i].m = ad[i].m; pr[i].v = ad[i].v; pr[i].sh = ad[i].sh;
@@ -483,14 +483,12 @@ void gemm_dw_batch(const std::vector<at::Tensor>& As, const std::vector<at::Tens
     if (!decay.empty()) need_decays(decay, n, "gemm_dw_batch decay");
     if (!bias_decay.empty()) need_decays(bias_decay, n, "gemm_dw_batch bias_decay");
     for (size_t i = 0; i < n; ++i) {
-      pr[i].wd = decay.empty() ? ad[0].wd : (float)decay[i];
-      pr[i].bias_wd = bias_decay.empty() ? ad[0].wd : (float)bias_decay[i];
+      pr[i].wd = decay.empty() ? hy.wd : (float)decay[i];
+      pr[i].bias_wd = bias_decay.empty() ? hy.wd : (float)bias_decay[i];
     }
     for (size_t i = 0; i < n && !anchor.empty(); ++i)
       pr[i].anchor = need_anchor(prox_mu, anchor[i], adam[4 * i], "gemm_dw_batch");
     step = ad[0].step;
-    hyper[0] = ad[0].lr; hyper[1] = ad[0].b1; hyper[2] = ad[0].b2; hyper[3] = ad[0].eps; hyper[4] = ad[0].wd;
-    hyper[5] = (float)ad[0].decoupled;
   }
   TORCH_CHECK(!adam.empty() || (decay.empty() && bias_decay.empty()),
               "gemm_dw_batch: weight decays need the fused Adam");
@@ -522,7 +520,7 @@ void gemm_dw_batch(const std::vector<at::Tensor>& As, const std::vector<at::Tens
       rs.run_wd = rest_wd->data_ptr<float>();
     }
     TORCH_CHECK(std::isfinite(word_wd) && word_wd >= 0.0, "gemm_dw_batch: word_wd must be finite and >= 0");
-    TORCH_CHECK(word_wd == 0.0 || (rest.size() == 8 && hp[5] != 0.0),
+    TORCH_CHECK(word_wd == 0.0 || (rest.size() == 8 && hy.decoupled),
                 "gemm_dw_batch: a decaying sparse word table needs its row flags and decoupled decay");
     rs.wwd = (float)word_wd;
     if (!anchor.empty()) rs.anchor = need_anchor(prox_mu, anchor[n], rest[0], "gemm_dw_batch rest");
@@ -545,8 +543,8 @@ void gemm_dw_batch(const std::vector<at::Tensor>& As, const std::vector<at::Tens
                     "gemm_dw_batch: an in-launch bias Adam needs the bias gradient inside the grad arena");
       }
   }
-  check_rc(fd_gemm_dw_batch((int)n, pr.data(), (int)K, step, adam.empty() ? nullptr : hyper, (int)cfg,
-                            rest.empty() ? nullptr : &rs, &sc, (float)prox_mu, stream()),
+  check_rc(fd_gemm_dw_batch((int)n, pr.data(), (int)K, step, adam.empty() ? nullptr : &hy, (int)cfg,
+                            rest.empty() ? nullptr : &rs, stream()),
            "gemm_dw_batch");
 }
 
@@ -1619,15 +1617,14 @@ void adam(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, const a
           int64_t run_total4, int64_t run_end4, const c10::optional<at::Tensor>& run_wd = c10::nullopt,
           const std::vector<double>& run_wd_host = {}, const std::vector<int64_t>& sched = {},
           double prox_mu = 0.0, const c10::optional<at::Tensor>& anchor = c10::nullopt) {
-  // sched: the learning-rate schedule whose base rate lr is (need_sched; empty = constant)
-  const FdLrSched sc = need_sched(sched, lr, "adam");
+  // sched: the learning-rate schedule whose base rate lr is (empty = constant)
+  const FdAdamHyper h = need_hyper(lr, b1, b2, eps, wd, decoupled, sched, prox_mu, "adam");
   // prox_mu / anchor: the FedProx term (adam_elem); the anchor is laid out like p
   const float* anc = need_anchor(prox_mu, anchor, p, "adam");
   TORCH_CHECK(prox_mu == 0.0 || wd == 0.0 || !(touched.has_value() && touched->defined()),
               "adam: row flags with weight decay take no proximal term");
   // run_wd: per-run weight decay (device fp32 [nruns], parameter groups) with the same values in
   // run_wd_host, checked here; none = wd for every run
-  TORCH_CHECK(std::isfinite(wd) && wd >= 0.0, "adam: weight decay must be finite and >= 0");
   need_opt(touched, at::kByte, "touched");
   need_opt(now, at::kByte, "now");
   if (touched.has_value() && touched->defined()) {
@@ -1671,9 +1668,9 @@ void adam(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, const a
   if (touched.has_value() && touched->defined())
     TORCH_CHECK(wd == 0.0 || decoupled, "adam: row flags with weight decay need decoupled decay");
   check_rc(fd_adam(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
-                   ptr<void>(shadow), n, step.data_ptr<int>(), (float)lr, (float)b1, (float)b2, (float)eps, (float)wd,
-                   decoupled ? 1 : 0, ptr<const unsigned char>(touched), ptr<const unsigned char>(now), skip_off,
-                   skip_rows, (int)row_len, rp, nruns, total4, rwd, &sc, (float)prox_mu, anc, stream()),
+                   ptr<void>(shadow), n, step.data_ptr<int>(), &h, ptr<const unsigned char>(touched),
+                   ptr<const unsigned char>(now), skip_off, skip_rows, (int)row_len, rp, nruns, total4, rwd, anc,
+                   stream()),
            "adam");
 }
 
@@ -1685,11 +1682,10 @@ void adam_rows(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, co
                double eps, const at::Tensor& ever, const c10::optional<at::Tensor>& now, int64_t row_len,
                double wd = 0.0, bool decoupled = false, const std::vector<int64_t>& sched = {},
                double prox_mu = 0.0, const c10::optional<at::Tensor>& anchor = c10::nullopt) {
-  const FdLrSched sc = need_sched(sched, lr, "adam_rows");
+  const FdAdamHyper h = need_hyper(lr, b1, b2, eps, wd, decoupled, sched, prox_mu, "adam_rows");
   // prox_mu / anchor: the FedProx term (adam_elem); the anchor is the table's, laid out like p
   const float* anc = need_anchor(prox_mu, anchor, p, "adam_rows");
   TORCH_CHECK(prox_mu == 0.0 || wd == 0.0, "adam_rows: a decaying table takes no proximal term");
-  TORCH_CHECK(std::isfinite(wd) && wd >= 0.0, "adam_rows: weight decay must be finite and >= 0");
   TORCH_CHECK(wd == 0.0 || decoupled, "adam_rows: weight decay needs decoupled decay");
   need(p, at::kFloat, "p");
   need(g, at::kFloat, "g");
@@ -1707,9 +1703,8 @@ void adam_rows(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, co
   TORCH_CHECK(ever.numel() >= rows, "adam_rows: ever flags");
   if (now.has_value() && now->defined()) TORCH_CHECK(now->numel() >= rows, "adam_rows: now flags");
   check_rc(fd_adam_rows(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
-                        ptr<void>(shadow), (int)rows, (int)row_len, step.data_ptr<int>(), (float)lr, (float)b1,
-                        (float)b2, (float)eps, ever.data_ptr<unsigned char>(), ptr<const unsigned char>(now),
-                        (float)wd, decoupled ? 1 : 0, &sc, (float)prox_mu, anc, stream()),
+                        ptr<void>(shadow), (int)rows, (int)row_len, step.data_ptr<int>(), &h,
+                        ever.data_ptr<unsigned char>(), ptr<const unsigned char>(now), anc, stream()),
            "adam_rows");
 }
 
@@ -1722,13 +1717,12 @@ void adam_lazy_decay(const at::Tensor& p, const c10::optional<at::Tensor>& shado
                      int64_t row_len, const c10::optional<at::Tensor>& ids,
                      const std::vector<int64_t>& sched = {}) {
   // sched: each missed step's multiplication takes the learning rate of its own step
-  const FdLrSched sc = need_sched(sched, lr, "adam_lazy_decay");
+  const FdAdamHyper h = need_hyper(lr, 0.0, 0.0, 0.0, wd, true, sched, 0.0, "adam_lazy_decay");
   need(p, at::kFloat, "p");
   need_opt(shadow, at::kBFloat16, "shadow");
   need(done, at::kInt, "done");
   need(ever, at::kByte, "ever");
   need(step, at::kInt, "step");
-  TORCH_CHECK(std::isfinite(wd) && wd >= 0.0 && std::isfinite(lr), "adam_lazy_decay: lr / weight decay");
   TORCH_CHECK(adj == 0 || adj == 1, "adam_lazy_decay: adj is 0 or 1");
   const int64_t n = p.numel();
   TORCH_CHECK(row_len > 0 && row_len % 4 == 0 && n > 0 && n % row_len == 0,
@@ -1750,7 +1744,7 @@ void adam_lazy_decay(const at::Tensor& p, const c10::optional<at::Tensor>& shado
   }
   check_rc(fd_adam_lazy_decay(p.data_ptr<float>(), ptr<void>(shadow), done.data_ptr<int>(),
                               ever.data_ptr<unsigned char>(), (int)rows, (int)row_len, step.data_ptr<int>(), (int)adj,
-                              (float)lr, (float)wd, idp, ids64, nids, &sc, stream()),
+                              &h, idp, ids64, nids, stream()),
            "adam_lazy_decay");
 }
 
@@ -1760,7 +1754,8 @@ void lr_schedule_table(const at::Tensor& out, double lr, const std::vector<int64
   need(out, at::kFloat, "out");
   TORCH_CHECK(out.numel() > 0 && out.numel() < (int64_t(1) << 30), "lr_schedule_table: 1 .. 2^30 steps");
   TORCH_CHECK(sched.size() == 4, "lr_schedule_table: sched is [kind, warmup, total, offset]");
-  const FdLrSched sc = need_sched(sched, lr, "lr_schedule_table");
+  TORCH_CHECK(std::isfinite(lr), "lr_schedule_table: lr must be finite");
+  const FdLrSched sc = need_sched(sched, "lr_schedule_table");
   check_rc(fd_lr_schedule_table(out.data_ptr<float>(), (int)out.numel(), (float)lr, &sc, stream()),
            "lr_schedule_table");
 }

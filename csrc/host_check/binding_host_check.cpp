@@ -36,17 +36,13 @@ void span(const void* p, long long bytes, const char* what) {
   violations.push_back(std::string("out of bounds: ") + what + " (" + std::to_string(bytes) + " B)");
 }
 void opt_span(const void* p, long long bytes, const char* what) { if (p) span(p, bytes, what); }
-// a learning-rate schedule as the kernels take it (adam_common.h adam_lr_at: int32 arithmetic)
-void sched(const FdLrSched* s, const char* what) {
-  if (!s) return;
-  const int lim = 1 << 30;
-  if (s->kind < 0 || s->kind > 2 || s->warmup < 0 || s->total < 0 || s->offset < 0 || s->warmup >= lim ||
-      s->total >= lim || s->offset >= lim || (s->kind == 1 && s->warmup > s->total))
-    violations.push_back(std::string(what) + ": learning-rate schedule out of range");
-}
-// a FedProx coefficient as the kernels take it (adam_common.h adam_elem)
-void mu(float m, const char* what) {
-  if (!(m >= 0.f) || !std::isfinite(m)) violations.push_back(std::string(what) + ": negative / non-finite prox_mu");
+// the hyper-parameters of an Adam step as the real launchers check them first (adam_epi.h
+// fd_adam_hyper_rc): the stubs stand for the launchers, so a descriptor one of them would refuse is a
+// violation -- the binding let it through
+void hyper(const FdAdamHyper* h, const char* what) {
+  if (!h) violations.push_back(std::string(what) + ": no hyper-parameters");
+  else if (const int rc = fd_adam_hyper_rc(h))
+    violations.push_back(std::string(what) + ": hyper-parameters out of range (rc=" + std::to_string(rc) + ")");
 }
 }  // namespace hc
 
@@ -124,18 +120,16 @@ int fd_gemm_dw2(const void* A0, const void* B0, float* C0, int M0, int N0, const
   return 0;
 }
 int fd_gemm_dw2_splits(int, int, int, int, int) { return 1; }
-int fd_gemm_dw_batch(int n, const FdDwProb* probs, int K, const int* step, const float* hyper, int cfg,
-                     const FdAdamRest* rest, const FdLrSched* sched, float prox_mu, hipStream_t) {
+int fd_gemm_dw_batch(int n, const FdDwProb* probs, int K, const int* step, const FdAdamHyper* h, int cfg,
+                     const FdAdamRest* rest, hipStream_t) {
   ++hc::calls;
-  hc::sched(sched, "dw_batch");
-  hc::mu(prox_mu, "dw_batch");
-  if (prox_mu != 0.f && !hyper) hc::violations.push_back("dw_batch: a proximal term without the fused Adam");
-  if (sched && sched->kind != 0 && !hyper) hc::violations.push_back("dw_batch: a schedule without the fused Adam");
+  if (h) hc::hyper(h, "dw_batch");  // (nullptr: no fused Adam -- and so neither a schedule nor a proximal term)
+  const float prox_mu = h ? h->mu : 0.f;
   if (rest) {
-    if (!hyper || !step) hc::violations.push_back("dw_batch rest without the fused Adam");
+    if (!h || !step) hc::violations.push_back("dw_batch rest without the fused Adam");
     if (rest->runs) hc::span(rest->runs, (long long)rest->nruns * 3 * 8, "dw_batch rest runs");
     if (rest->run_wd) hc::span(rest->run_wd, (long long)rest->nruns * 4, "dw_batch rest run decays");
-    if (rest->wwd != 0.f && (!rest->ever || !hyper || hyper[5] == 0.f))
+    if (rest->wwd != 0.f && (!rest->ever || !h || !h->decoupled))
       hc::violations.push_back("dw_batch: a decaying sparse word table without flags / decoupled decay");
     if (rest->ever) {
       hc::span(rest->ever, rest->wrows, "dw_batch rest ever");
@@ -169,7 +163,7 @@ int fd_gemm_dw_batch(int n, const FdDwProb* probs, int K, const int* step, const
       if (prox_mu != 0.f && q.bias && rest && rest->anchor && rest->g)
         hc::span(rest->anchor + (q.bias - rest->g), (long long)q.M * 4, "dw_batch bias anchor");
       hc::span(step, 4, "dw_batch step");
-      if (!hyper) hc::violations.push_back("dw_batch: fused Adam without hyper-parameters");
+      if (!h) hc::violations.push_back("dw_batch: fused Adam without hyper-parameters");
       if (!(q.wd >= 0.f) || !(q.bias_wd >= 0.f)) hc::violations.push_back("dw_batch: negative / NaN weight decay");
     } else {
       hc::span(q.C, mn * 4, "dw_batch C");
@@ -179,11 +173,13 @@ int fd_gemm_dw_batch(int n, const FdDwProb* probs, int K, const int* step, const
   return 0;
 }
 int fd_adam_rows(float* p, const float* g, float* m, float* v, void* shadow, int rows, int row_len, const int* step,
-                 float, float, float, float, const unsigned char* ever, const unsigned char* now, float wd,
-                 int decoupled, const FdLrSched* sched, float prox_mu, const float* anchor, hipStream_t) {
+                 const FdAdamHyper* h, const unsigned char* ever, const unsigned char* now, const float* anchor,
+                 hipStream_t) {
   ++hc::calls;
-  hc::sched(sched, "adam_rows");
-  hc::mu(prox_mu, "adam_rows");
+  hc::hyper(h, "adam_rows");
+  if (!h) return 0;
+  const float wd = h->wd, prox_mu = h->mu;
+  const int decoupled = h->decoupled;
   if (prox_mu != 0.f) hc::span(anchor, (long long)rows * row_len * 4, "adam_rows anchor");
   if (prox_mu != 0.f && wd != 0.f) hc::violations.push_back("adam_rows: a proximal term on a decaying table");
   if (wd != 0.f && !decoupled) hc::violations.push_back("adam_rows: coupled weight decay on flagged rows");
@@ -199,10 +195,10 @@ int fd_adam_rows(float* p, const float* g, float* m, float* v, void* shadow, int
   return 0;
 }
 int fd_adam_lazy_decay(float* p, void* shadow, int* done, const unsigned char* ever, int rows, int row_len,
-                       const int* step, int adj, float, float wd, const void* ids, int ids64, long long n,
-                       const FdLrSched* sched, hipStream_t) {
+                       const int* step, int adj, const FdAdamHyper* h, const void* ids, int ids64, long long n,
+                       hipStream_t) {
   ++hc::calls;
-  hc::sched(sched, "lazy decay");
+  hc::hyper(h, "lazy decay");
   const long long tot = (long long)rows * row_len;
   hc::span(p, tot * 4, "lazy decay p");
   hc::opt_span(shadow, tot * 2, "lazy decay shadow");
@@ -210,7 +206,7 @@ int fd_adam_lazy_decay(float* p, void* shadow, int* done, const unsigned char* e
   hc::span(ever, rows, "lazy decay ever");
   hc::span(step, 4, "lazy decay step");
   if (ids) hc::span(ids, n * (ids64 ? 8 : 4), "lazy decay ids");
-  if (adj < 0 || adj > 1 || !(wd >= 0.f)) hc::violations.push_back("lazy decay: adj / weight decay");
+  if (adj < 0 || adj > 1) hc::violations.push_back("lazy decay: adj");
   return 0;
 }
 int fd_gemm_splitk(int epi, const void* A, const void* Bt, int M, int N, int K, float* workspace,
@@ -615,14 +611,13 @@ int fd_eval_metrics(const float*, const long long*, int, double*, long long*, fl
   ++hc::calls;
   return 0;
 }
-int fd_adam(float* p, const float* g, float* m, float* v, void* shadow, long long n, const int* step, float, float,
-            float, float, float, int, const unsigned char* touched, const unsigned char* now, long long skip_off,
+int fd_adam(float* p, const float* g, float* m, float* v, void* shadow, long long n, const int* step,
+            const FdAdamHyper* h, const unsigned char* touched, const unsigned char* now, long long skip_off,
             long long skip_rows, int row_len, const long long* runs, int nruns, long long run_total4,
-            const float* run_wd, const FdLrSched* sched, float prox_mu, const float* anchor, hipStream_t) {
+            const float* run_wd, const float* anchor, hipStream_t) {
   ++hc::calls;
-  hc::sched(sched, "adam");
-  hc::mu(prox_mu, "adam");
-  if (prox_mu != 0.f) hc::span(anchor, n * 4, "adam anchor");
+  hc::hyper(h, "adam");
+  if (h && h->mu != 0.f) hc::span(anchor, n * 4, "adam anchor");
   if (run_wd) {
     if (!runs) hc::violations.push_back("adam: run decays without a run table");
     hc::span(run_wd, (long long)nruns * 4, "adam run decays");
@@ -653,8 +648,8 @@ int fd_adam(float* p, const float* g, float* m, float* v, void* shadow, long lon
 }
 int fd_lr_schedule_table(float* out, int n, float lr, const FdLrSched* sched, hipStream_t) {
   ++hc::calls;
-  hc::sched(sched, "lr table");
   if (!sched) hc::violations.push_back("lr table: no schedule");
+  else if (fd_lr_sched_rc(sched)) hc::violations.push_back("lr table: learning-rate schedule out of range");
   if (!std::isfinite(lr)) hc::violations.push_back("lr table: lr");
   hc::span(out, (long long)n * 4, "lr table out");
   return 0;
@@ -1166,6 +1161,65 @@ int main() {
     expect_reject("lr table lr NaN", [&] { lr_schedule_table(T_({4}, f32), std::nan(""), lin); });
     expect_reject("lr table empty", [&] { lr_schedule_table(T_({0}, f32), 2e-5, lin); });
     expect_reject("lr table no schedule", [&] { lr_schedule_table(T_({4}, f32), 2e-5, {}); });
+  }
+  // ---- invalid hyper-parameters: ONE table against every entry that builds an FdAdamHyper (adam,
+  // adam_rows, adam_lazy_decay, gemm_dw_batch with and without the rest of the step).  Each entry
+  // first accepts the table's base values with the very tensors the rows use, so a rejection is the
+  // row's doing; each row must then be refused before any launcher call.  (adam_lazy_decay takes
+  // no proximal term: the mu rows do not apply to it.)
+  {
+    const int64_t n = 4096, an = 64 * 64 + 1024;
+    auto p = T_({n}, f32), g = T_({n}, f32), m = T_({n}, f32), v = T_({n}, f32), sh = T_({n}, bf), step = T_({1}, i32);
+    auto ever = T_({64}, at::kByte), now = T_({64}, at::kByte), done = T_({64}, i32);
+    const c10::optional<at::Tensor> anc = T_({n}, f32);
+    std::vector<at::Tensor> As = {T_({64, 128}, bf)}, Bs = {T_({64, 64}, bf)}, Cs = {T_({128, 64}, f32)};
+    std::vector<at::Tensor> st = {T_({128 * 64}, f32), T_({128 * 64}, f32), T_({128 * 64}, f32), T_({128 * 64}, bf), step};
+    std::vector<at::Tensor> rest = {T_({an}, f32), T_({an}, f32), T_({an}, f32), T_({an}, f32), T_({an}, bf),
+                                    T_({2, 3}, i64), T_({64}, at::kByte), T_({64}, at::kByte)};
+    auto rp = rest[5].data_ptr<int64_t>();
+    rp[0] = 1024; rp[1] = 128; rp[2] = 0; rp[3] = 1152; rp[4] = 128; rp[5] = 128;
+    const std::vector<int64_t> ri = {256, 0, 64, 64}, acc = {0};
+    const std::vector<at::Tensor> danc = {T_({128 * 64}, f32)}, danc_rest = {danc[0], T_({an}, f32)};
+    struct Hyper { const char* name; double lr, wd, mu; std::vector<int64_t> sched; };
+    const double inf = HUGE_VAL, nan = std::nan("");
+    const int64_t lim = int64_t(1) << 30;
+    const Hyper base = {"base", 2e-5, 0.0, 0.05, {1, 3, 10, 0}};
+    const std::vector<Hyper> bad = {
+        {"mu negative", 2e-5, 0.0, -0.1, {}},          {"mu NaN", 2e-5, 0.0, nan, {}},
+        {"mu inf", 2e-5, 0.0, inf, {}},                {"wd negative", 2e-5, -0.01, 0.05, {}},
+        {"wd NaN", 2e-5, nan, 0.05, {}},               {"wd inf", 2e-5, inf, 0.05, {}},
+        {"lr inf", inf, 0.0, 0.05, {}},                {"lr -inf", -inf, 0.0, 0.05, {}},
+        {"lr NaN", nan, 0.0, 0.05, {}},                {"sched kind 3", 2e-5, 0.0, 0.05, {3, 0, 10, 0}},
+        {"sched kind -1", 2e-5, 0.0, 0.05, {-1, 0, 10, 0}}, {"sched warmup -1", 2e-5, 0.0, 0.05, {1, -1, 10, 0}},
+        {"sched total -10", 2e-5, 0.0, 0.05, {1, 2, -10, 0}}, {"sched offset -1", 2e-5, 0.0, 0.05, {1, 2, 10, -1}},
+        {"sched warmup > total", 2e-5, 0.0, 0.05, {1, 11, 10, 0}}, {"sched 3 entries", 2e-5, 0.0, 0.05, {1, 3, 10}},
+        {"sched total 2^31", 2e-5, 0.0, 0.05, {1, 0, int64_t(1) << 31, 0}},
+        {"sched total 2^30", 2e-5, 0.0, 0.05, {1, 0, lim, 0}}, {"sched warmup 2^30", 2e-5, 0.0, 0.05, {2, lim, 0, 0}},
+        {"sched offset 2^30", 2e-5, 0.0, 0.05, {1, 0, 10, lim}}};
+    // (decoupled decay throughout, so the base and the wd rows differ in nothing but the value)
+    auto e_adam = [&](const Hyper& h) { adam(p, g, m, v, sh, step, h.lr, 0.9, 0.999, 1e-8, h.wd, true, none, none, 0, 0,
+                                             4, none, 0, 0, none, {}, h.sched, h.mu, anc); };
+    auto e_rows = [&](const Hyper& h) { adam_rows(p, g, m, v, sh, step, h.lr, 0.9, 0.999, 1e-8, ever, now, 64, h.wd,
+                                                  true, h.sched, h.mu, anc); };
+    auto e_lazy = [&](const Hyper& h) { adam_lazy_decay(p, sh, done, ever, step, 0, h.lr, h.wd, 64, none, h.sched); };
+    auto e_dwb = [&](const Hyper& h) { gemm_dw_batch(As, Bs, Cs, acc, st, {h.lr, 0.9, 0.999, 1e-8, h.wd, 1.0}, -1, {},
+                                                     {}, {}, {}, {}, none, {}, 0.0, h.sched, h.mu, danc); };
+    auto e_dwb_rest = [&](const Hyper& h) { gemm_dw_batch(As, Bs, Cs, acc, st, {h.lr, 0.9, 0.999, 1e-8, h.wd, 1.0}, -1,
+                                                          {}, rest, ri, {}, {}, none, {}, 0.0, h.sched, h.mu,
+                                                          danc_rest); };
+    expect_ok("hyper table base: adam", [&] { e_adam(base); });
+    expect_ok("hyper table base: adam_rows", [&] { e_rows(base); });
+    expect_ok("hyper table base: adam_lazy_decay", [&] { e_lazy(base); });
+    expect_ok("hyper table base: dw_batch", [&] { e_dwb(base); });
+    expect_ok("hyper table base: dw_batch rest", [&] { e_dwb_rest(base); });
+    for (const Hyper& h : bad) {
+      const std::string nm = std::string("hyper table, ") + h.name + ": ";
+      expect_reject((nm + "adam").c_str(), [&] { e_adam(h); });
+      expect_reject((nm + "adam_rows").c_str(), [&] { e_rows(h); });
+      if (h.mu == base.mu) expect_reject((nm + "adam_lazy_decay").c_str(), [&] { e_lazy(h); });
+      expect_reject((nm + "dw_batch").c_str(), [&] { e_dwb(h); });
+      expect_reject((nm + "dw_batch rest").c_str(), [&] { e_dwb_rest(h); });
+    }
   }
   // ---- FedOpt server step: four fp32 streams, the bf16 shadow, two stats floats per block
   {

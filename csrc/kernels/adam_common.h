@@ -10,18 +10,19 @@
 // term -- the gradient gets mu * (p - a), a the element's anchor (its value when the round began),
 // taken from p as loaded, before a decoupled decay multiplies it: p.grad += mu * (p - p_global), then
 // torch.optim.Adam / AdamW.  With mu == 0 the anchor is never looked at (callers pass 0).
-DEV void adam_elem(float lr, float b1, float b2, float eps, float wd, int decoupled, float mu, float a, float& p,
-                   float g, float& m, float& v, float step_size, float inv_sqrt_bc2) {
+// h.lr: already this step's rate (adam_bias_corr); wd: the element's decay (h.wd is the launch's default).
+DEV void adam_elem(const FdAdamHyper& h, float wd, float a, float& p, float g, float& m, float& v, float step_size,
+                   float inv_sqrt_bc2) {
 #pragma clang fp contract(off)
   float gr = g;
-  if (mu != 0.f) gr += mu * (p - a);
+  if (h.mu != 0.f) gr += h.mu * (p - a);
   if (wd != 0.f) {
-    if (decoupled) p *= 1.f - lr * wd;
+    if (h.decoupled) p *= 1.f - h.lr * wd;
     else gr += wd * p;
   }
-  m = b1 * m + (1.f - b1) * gr;
-  v = b2 * v + (1.f - b2) * gr * gr;
-  const float denom = sqrtf(v) * inv_sqrt_bc2 + eps;
+  m = h.b1 * m + (1.f - h.b1) * gr;
+  v = h.b2 * v + (1.f - h.b2) * gr * gr;
+  const float denom = sqrtf(v) * inv_sqrt_bc2 + h.eps;
   p -= step_size * m / denom;
 }
 
@@ -57,12 +58,11 @@ DEV void adam_bias_corr(const int* step, float lr, float b1, float b2, float& st
   inv_sqrt_bc2 = 1.f / sqrtf(bc2);
 }
 
-// The same under a schedule with base rate lr; lr_t: this step's learning rate (adam_lr_at) -- both
-// step_size and the decoupled decay use it.
-DEV void adam_bias_corr(const int* step, float lr, const FdLrSched& sched, float b1, float b2, float& lr_t,
-                        float& step_size, float& inv_sqrt_bc2) {
-  lr_t = adam_lr_at(lr, sched, step[0]);
-  adam_bias_corr(step, lr_t, b1, b2, step_size, inv_sqrt_bc2);
+// The same for a launch's hyper-parameters as they arrive: h.lr, the base rate of h.sched, becomes this
+// step's rate (adam_lr_at; step_size and the decoupled decay use it).  Once per kernel, on its own copy.
+DEV void adam_bias_corr(const int* step, FdAdamHyper& h, float& step_size, float& inv_sqrt_bc2) {
+  h.lr = adam_lr_at(h.lr, h.sched, step[0]);
+  adam_bias_corr(step, h.lr, h.b1, h.b2, step_size, inv_sqrt_bc2);
 }
 
 struct AdamArgs {
@@ -73,8 +73,7 @@ struct AdamArgs {
   bf16_t* shadow;
   long long n4;
   const int* step;
-  float lr, b1, b2, eps, wd;
-  int decoupled;
+  FdAdamHyper h;                    // (adam_epi.h; h.lr: the base rate until adam_bias_corr resolves it)
   long long skip_off4, skip_end4;  // float4 range whose rows may be skipped
   int row4;                         // float4s per row in that range
   const unsigned char* touched;     // sticky row flags: nonzero Adam state (nullable)
@@ -87,13 +86,9 @@ struct AdamArgs {
   // Per-run weight decay, parallel to the run table (nullable = wd for every run): parameter
   // groups -- biases and LayerNorm affines usually decay by 0 (engine/optim.py no_decay).
   const float* run_wd;
-  // FedProx: mu != 0 adds mu * (p - anchor) to every gradient (adam_elem); anchor is laid out like p
-  // and only read when mu != 0 (nullable otherwise)
+  // FedProx: h.mu != 0 adds mu * (p - anchor) to every gradient (adam_elem); anchor is laid out like
+  // p and only read when h.mu != 0 (nullable otherwise)
   const float* anchor;
-  float mu;
-  // lr is the base rate of this schedule; a kernel replaces lr by the step's rate (adam_bias_corr)
-  // before the element loops
-  FdLrSched sched;
 };
 
 // virtual index -> arena float4 index through the run table (binary search on the prefix)
@@ -123,7 +118,7 @@ DEV void st_nt(float4* p, float4 v) {
 // float4 i of the anchor, read once per step (nontemporal) -- and only under a proximal term: the
 // branch is uniform over the launch, so mu == 0 adds no traffic.
 DEV float4 ld_anchor(const AdamArgs& a, long long i) {
-  return a.mu != 0.f ? ld_nt(reinterpret_cast<const float4*>(a.anchor) + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+  return a.h.mu != 0.f ? ld_nt(reinterpret_cast<const float4*>(a.anchor) + i) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
 // The Adam update of 4 elements (adam_elem each) with weight decay wd and anchor a4.
@@ -132,12 +127,7 @@ DEV void adam_math4(const AdamArgs& a, float wd, float (&pp)[4], const float (&g
   const float aa[4] = {a4.x, a4.y, a4.z, a4.w};
 #pragma unroll
   for (int e = 0; e < 4; ++e)
-    adam_elem(a.lr, a.b1, a.b2, a.eps, wd, a.decoupled, a.mu, aa[e], pp[e], gg[e], mm[e], vv[e], step_size,
-              inv_sqrt_bc2);
-}
-DEV void adam_math4(const AdamArgs& a, float (&pp)[4], const float (&gg)[4], float (&mm)[4], float (&vv)[4],
-                    float4 a4, float step_size, float inv_sqrt_bc2) {
-  adam_math4(a, a.wd, pp, gg, mm, vv, a4, step_size, inv_sqrt_bc2);
+    adam_elem(a.h, wd, aa[e], pp[e], gg[e], mm[e], vv[e], step_size, inv_sqrt_bc2);
 }
 
 // One flagged row of a [rows][row4] float4 table starting at float4 base4 (one wave; gradient 0
@@ -154,7 +144,7 @@ DEV void adam_row(const AdamArgs& a, long long base4, int row, int row4, int lan
     const float4 a4 = ld_anchor(a, i);
     float pp[4] = {p.x, p.y, p.z, p.w}, gg[4] = {g.x, g.y, g.z, g.w};
     float mm[4] = {m.x, m.y, m.z, m.w}, vv[4] = {v.x, v.y, v.z, v.w};
-    adam_math4(a, pp, gg, mm, vv, a4, step_size, inv_sqrt_bc2);
+    adam_math4(a, a.h.wd, pp, gg, mm, vv, a4, step_size, inv_sqrt_bc2);
     st_nt(reinterpret_cast<float4*>(a.p) + i, make_float4(pp[0], pp[1], pp[2], pp[3]));
     st_nt(reinterpret_cast<float4*>(a.m) + i, make_float4(mm[0], mm[1], mm[2], mm[3]));
     st_nt(reinterpret_cast<float4*>(a.v) + i, make_float4(vv[0], vv[1], vv[2], vv[3]));
@@ -168,7 +158,7 @@ template <bool NT, bool NTP>
 DEV void adam_flat4(const AdamArgs& a, long long vi, float step_size, float inv_sqrt_bc2) {
   int run = 0;
   const long long i = a.runs ? run_index(a.runs, a.nruns, vi, run) : vi;
-  const float wd = a.run_wd ? a.run_wd[run] : a.wd;
+  const float wd = a.run_wd ? a.run_wd[run] : a.h.wd;
   // Rows never touched since the moments were reset have m = v = g = 0: their
   // Adam update is exactly zero, so skip all their traffic (wd == 0 only).
   bool gvalid = true;
@@ -228,7 +218,7 @@ DEV void adam_row768(const AdamArgs& a, int row, int lane, float step_size, floa
     const long long i = (long long)row * 192 + lane + 64 * k;
     float pp[4] = {p[k].x, p[k].y, p[k].z, p[k].w}, gg[4] = {g[k].x, g[k].y, g[k].z, g[k].w};
     float mm[4] = {m[k].x, m[k].y, m[k].z, m[k].w}, vv[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
-    adam_math4(a, pp, gg, mm, vv, an[k], step_size, inv_sqrt_bc2);
+    adam_math4(a, a.h.wd, pp, gg, mm, vv, an[k], step_size, inv_sqrt_bc2);
     st_nt(reinterpret_cast<float4*>(a.p) + i, make_float4(pp[0], pp[1], pp[2], pp[3]));
     st_nt(reinterpret_cast<float4*>(a.m) + i, make_float4(mm[0], mm[1], mm[2], mm[3]));
     st_nt(reinterpret_cast<float4*>(a.v) + i, make_float4(vv[0], vv[1], vv[2], vv[3]));

@@ -14,6 +14,33 @@
 // graph replays the whole ramp.
 struct FdLrSched { int kind; int warmup; int total; int offset; };   // kind 0 = constant
 
+// The hyper-parameters of one Adam step: what every launch that applies Adam takes (by pointer in
+// the fd_* launchers, by value inside their kernel arguments).  State -- p / m / v / shadow, the
+// step counter, the FedProx anchor -- stays beside it.
+struct FdAdamHyper {
+  float lr, b1, b2, eps, wd;   // lr: base rate of sched; wd: the launch's default decay
+  int decoupled;               // AdamW-style decay
+  FdLrSched sched;             // kind 0 = constant
+  float mu;                    // FedProx coefficient, 0 = none
+};
+
+// The ranges the kernels take: 0, or the code of the first rule broken (above the launchers' own
+// 1..9).  Every launcher that takes an FdAdamHyper calls fd_adam_hyper_rc first; the binding calls it
+// to refuse a call before any launch.  (2^30: adam_lr_at's offset + step and total - warmup are int32.)
+static inline int fd_lr_sched_rc(const FdLrSched* s) {
+  const unsigned lim = 1u << 30;  // (unsigned compares: a negative number fails them too)
+  if (s->kind < 0 || s->kind > 2) return 13;
+  if ((unsigned)s->warmup >= lim || (unsigned)s->total >= lim || (unsigned)s->offset >= lim) return 14;
+  return s->kind == 1 && s->warmup > s->total ? 15 : 0;
+}
+static inline int fd_adam_hyper_rc(const FdAdamHyper* h) {
+  if (!h) return 10;
+  if (!__builtin_isfinite(h->lr)) return 11;
+  if (!__builtin_isfinite(h->wd) || !(h->wd >= 0.f)) return 12;
+  if (!__builtin_isfinite(h->mu) || !(h->mu >= 0.f)) return 16;
+  return fd_lr_sched_rc(&h->sched);
+}
+
 struct FdAdamEpi {
   float* p;           // fp32 master (nullptr = no fused optimizer)
   float* m;           // first moment

@@ -102,6 +102,8 @@ struct GemmParams {
   const float* acol_a;   // the bias's FedProx anchor (read only when adam.mu != 0)
   int ln2_half;          // EPI_LN2*: this block's K half and the 64-column half of the tile it finishes
 };
+// (growing it moves SGPR spills in kernels that never read the new fields: profiles/fedprox_kernel_resources.txt)
+static_assert(sizeof(GemmParams) == 440, "GemmParams is the by-value argument of every GEMM instantiation");
 
 constexpr int BKT = 64;
 constexpr int LDS_MAX = 163840;
@@ -277,6 +279,11 @@ DEV void st_nt4(float* p, float4 v) {
   __builtin_nontemporal_store(f32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4*>(p));
 }
 
+// An FdAdamEpi's hyper-parameters as adam_elem takes them; mu: a.mu (PROX kernels) or a constant 0.
+DEV FdAdamHyper epi_hyper(const FdAdamEpi& a, float mu) {
+  return FdAdamHyper{a.lr, a.b1, a.b2, a.eps, a.wd, a.decoupled, FdLrSched{}, mu};
+}
+
 // Adam on 4 consecutive elements of a finished gradient tile: adam_elem (adam_common.h), as in
 // adam_kernel (head_optim.hip), so a fused step matches the unfused one bitwise.
 // PROX (EPI_F32P): the launch may carry a FedProx term.
@@ -285,15 +292,13 @@ DEV float4 adam_epi4(const FdAdamEpi& a, size_t i, float4 g4, float step_size, f
   const float4 p4 = ld_nt4(a.p + i), m4 = ld_nt4(a.m + i), v4 = ld_nt4(a.v + i);
   // the FedProx anchor: read once per step like m / v, and only under a proximal term (uniform
   // over the launch: mu == 0 adds no traffic)
-  const float mu = PROX ? a.mu : 0.f;
-  const float4 a4 = mu != 0.f ? ld_nt4(a.anchor + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+  const FdAdamHyper h = epi_hyper(a, PROX ? a.mu : 0.f);
+  const float4 a4 = h.mu != 0.f ? ld_nt4(a.anchor + i) : make_float4(0.f, 0.f, 0.f, 0.f);
   float pp[4] = {p4.x, p4.y, p4.z, p4.w}, gg[4] = {g4.x, g4.y, g4.z, g4.w};
   float mm[4] = {m4.x, m4.y, m4.z, m4.w}, vv[4] = {v4.x, v4.y, v4.z, v4.w};
   const float aa[4] = {a4.x, a4.y, a4.z, a4.w};
 #pragma unroll
-  for (int e = 0; e < 4; ++e)
-    adam_elem(a.lr, a.b1, a.b2, a.eps, a.wd, a.decoupled, mu, aa[e], pp[e], gg[e], mm[e], vv[e], step_size,
-              inv_sqrt_bc2);
+  for (int e = 0; e < 4; ++e) adam_elem(h, a.wd, aa[e], pp[e], gg[e], mm[e], vv[e], step_size, inv_sqrt_bc2);
   st_nt4(a.p + i, make_float4(pp[0], pp[1], pp[2], pp[3]));
   st_nt4(a.m + i, make_float4(mm[0], mm[1], mm[2], mm[3]));
   st_nt4(a.v + i, make_float4(vv[0], vv[1], vv[2], vv[3]));
@@ -319,13 +324,7 @@ DEV void f32_epilogue(const GemmParams& p, const char* smem, int ldc_lds, int m0
   }
   const bool adam = p.adam.p != nullptr;
   float step_size = 0.f, inv_sqrt_bc2 = 0.f;
-  if (adam) {
-    const int t = p.adam.step[0];
-    const float bc1 = 1.f - powf(p.adam.b1, (float)t);
-    const float bc2 = 1.f - powf(p.adam.b2, (float)t);
-    step_size = p.adam.lr / bc1;
-    inv_sqrt_bc2 = 1.f / sqrtf(bc2);
-  }
+  if (adam) adam_bias_corr(p.adam.step, p.adam.lr, p.adam.b1, p.adam.b2, step_size, inv_sqrt_bc2);
 #pragma unroll 2
   for (int id = tid; id < BM * CPR; id += NT) {
     const int r = id / CPR, cc = id - r * CPR;
@@ -1289,8 +1288,7 @@ DEV void gemm_tile_at(const GemmParams& p, int tm, int tn, char* smem) {
               mu = p.adam.mu;
               if (mu != 0.f) ab = p.acol_a[m];
             }
-            adam_elem(p.adam.lr, p.adam.b1, p.adam.b2, p.adam.eps, p.acol_wd, p.adam.decoupled, mu, ab, pb, s, mb, vb,
-                      ss, inv);
+            adam_elem(epi_hyper(p.adam, mu), p.acol_wd, ab, pb, s, mb, vb, ss, inv);
             p.acol_p[m] = pb;
             p.acol_m[m] = mb;
             p.acol_v[m] = vb;
@@ -1802,10 +1800,7 @@ struct DwBatch {
   int n, K, ntiles, group_m;
   int diag;  // FD_GEMM_DIAG (profiling only)
   const int* step;
-  float lr, b1, b2, eps, wd;
-  int decoupled;
-  FdLrSched sched;  // lr is its base rate (adam_common.h adam_lr_at)
-  float mu;         // FedProx (adam_elem): != 0 -> every problem with p and the rest carry an anchor
+  FdAdamHyper h;    // of the fused step (adam_epi.h); h.mu != 0 -> every problem with p and the rest carry an anchor
   FdAdamRest rest;  // rest.p != nullptr: blocks [ntiles, ntiles + rest blocks) finish the optimizer step
   // Mixed schedule (fd_gemm_dw_batch plan_dwb_mix; mixed != 0): problems are ordered in three classes
   // -- [long 256 x 256 | long 256 x 128 (half) | short-K 256 x 256] -- and each class is dealt to the
@@ -1815,6 +1810,7 @@ struct DwBatch {
   int mixed;
   int cls_tiles[3], cls_off[3], cls_pad[3];
 };
+static_assert(sizeof(DwBatch) <= 4096, "DwBatch is a by-value kernel argument: the kernel-argument limit");
 
 // The mixed schedule's half tiles: 256 x 128 on the same 8 waves (4 x 2, 64 x 64 per wave).  Every
 // output element runs the same K-step / MFMA chain as in a 256 x 256 tile and the same f32_epilogue
@@ -1842,19 +1838,15 @@ DEV void dwb_tile(const DwBatch& bt, int lid, char* smem) {
   p.accumulate = q.accumulate;
   p.acol = q.bias;
   if (q.p) {
-    p.adam.p = q.p; p.adam.m = q.m; p.adam.v = q.v; p.adam.sh = q.sh; p.adam.step = bt.step;
-    p.adam.lr = bt.lr; p.adam.b1 = bt.b1; p.adam.b2 = bt.b2; p.adam.eps = bt.eps; p.adam.wd = q.wd;
-    p.adam.decoupled = bt.decoupled;
-    if constexpr (PROX) {
-      p.adam.mu = bt.mu;
-      p.adam.anchor = q.anchor;
-    }
+    const FdAdamHyper& h = bt.h;
+    p.adam = FdAdamEpi{q.p, q.m, q.v, q.sh, bt.step, h.lr, h.b1, h.b2, h.eps, q.wd, h.decoupled,
+                       PROX ? q.anchor : nullptr, PROX ? h.mu : 0.f};
     // A scheduled rate is resolved here, once per thread and outside the K loop (uniform: kept in a
     // scalar register), so the epilogues -- shared with the launches that take a plain rate -- read
     // this step's rate from p.adam.lr.  The constant schedule leaves the rate as it came.
-    if (bt.sched.kind != 0)
+    if (h.sched.kind != 0)
       p.adam.lr = __int_as_float(
-          __builtin_amdgcn_readfirstlane(__float_as_int(adam_lr_at(bt.lr, bt.sched, bt.step[0]))));
+          __builtin_amdgcn_readfirstlane(__float_as_int(adam_lr_at(h.lr, h.sched, bt.step[0]))));
     if (q.bias && bt.rest.p) {  // the qkv bias's state lies at its gradient's arena offset
       const ptrdiff_t off = q.bias - bt.rest.g;
       p.acol_p = bt.rest.p + off; p.acol_m = bt.rest.m + off; p.acol_v = bt.rest.v + off;
@@ -1894,15 +1886,15 @@ constexpr int DWB_RUNS_LDS = 4096;  // run-table entries (3 per run) staged in L
 template <int NT, bool PROX>
 DEV void dwb_rest(const DwBatch& bt, int rb, char* smem) {
   const FdAdamRest& r = bt.rest;
-  float lr_t, ss, inv;
-  adam_bias_corr(bt.step, bt.lr, bt.sched, bt.b1, bt.b2, lr_t, ss, inv);
   AdamArgs a{};
-  a.step = bt.step; a.lr = lr_t; a.b1 = bt.b1; a.b2 = bt.b2; a.eps = bt.eps;
-  a.mu = PROX ? bt.mu : 0.f;  // (a constant 0 folds every anchor load away: adam_common.h ld_anchor)
+  a.step = bt.step;
+  a.h = bt.h;
+  a.h.mu = PROX ? bt.h.mu : 0.f;  // (a constant 0 folds every anchor load away: adam_common.h ld_anchor)
+  float ss, inv;
+  adam_bias_corr(bt.step, a.h, ss, inv);
   if (rb < r.flat_blocks) {
     a.p = r.p; a.g = r.g; a.m = r.m; a.v = r.v; a.shadow = reinterpret_cast<bf16_t*>(r.sh);
     a.anchor = r.anchor;
-    a.wd = bt.wd; a.decoupled = bt.decoupled;
     a.runs = r.runs; a.nruns = r.nruns; a.n4 = r.n4;
     a.run_wd = r.run_wd;
     // adam_flat4's element body (the same arithmetic, bitwise), U float4 per thread at once: the
@@ -1926,7 +1918,7 @@ DEV void dwb_rest(const DwBatch& bt, int rb, char* smem) {
         const long long vi = min(v0 + u * stride, r.n4 - 1);
         int run = 0;
         idx[u] = a.runs ? run_index(a.runs, a.nruns, vi, run) : vi;
-        wd[u] = a.run_wd ? a.run_wd[run] : a.wd;
+        wd[u] = a.run_wd ? a.run_wd[run] : a.h.wd;
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -1956,7 +1948,7 @@ DEV void dwb_rest(const DwBatch& bt, int rb, char* smem) {
   a.p = r.p + r.woff; a.g = r.g + r.woff; a.m = r.m + r.woff; a.v = r.v + r.woff;
   a.shadow = r.sh ? reinterpret_cast<bf16_t*>(r.sh) + r.woff : nullptr;
   a.anchor = r.anchor ? r.anchor + r.woff : nullptr;
-  a.wd = r.wwd; a.decoupled = bt.decoupled;  // (wwd != 0: decoupled only, the other rows decay lazily)
+  a.h.wd = r.wwd;  // (wwd != 0: decoupled only, the other rows decay lazily)
   a.touched = r.ever; a.now = r.now;
   const int lane = threadIdx.x & 63;
   const int nwaves = r.row_blocks * (NT / 64);
@@ -2566,7 +2558,7 @@ int fd_gemm_dw2(const void* A0, const void* B0, float* C0, int M0, int N0, const
 }
 
 // All-layer weight gradients in one launch (gemm_dw_batch_kernel).  probs[i] = {A, B, C, p, m,
-// v, sh, M, N, -, accumulate} (tile0 is filled here); adam != nullptr -> hyper-parameters of
+// v, sh, M, N, -, accumulate} (tile0 is filled here); h != nullptr -> hyper-parameters of
 // the fused optimizer step for the problems with p != nullptr.  cfg < 0: FD_GEMM_DWB_CFG or
 // the default 256 x 256 (2 x 4 waves, 2-deep ring, banded fp32 epilogue; falls back to 128 x 64
 // when a shape is not a multiple of 256).  Measured (profiles/r2_dw_batch_isolated_cfgs.txt,
@@ -2587,7 +2579,7 @@ bool dwb_launch_cfg(int id, DwBatch& bt, hipStream_t st, bool dry) {
     return true;
   };
   if (bt.mixed && id != 11) return false;
-  if (bt.mu != 0.f) {  // the FedProx arm of each configuration (the same tiles, anchors in the epilogues)
+  if (bt.h.mu != 0.f) {  // the FedProx arm of each configuration (the same tiles, anchors in the epilogues)
     switch (id) {
       case 1: return go(gemm_dw_batch_kernel<128, 128, 2, 2, 2, BKT, false, true>, 128, 128, 256);
       case 8: return go(gemm_dw_batch_kernel<128, 64, 2, 2, 2, BKT, false, true>, 128, 64, 256);
@@ -2706,25 +2698,24 @@ bool plan_dwb_mix(DwBatch& bt, int mode) {
   return true;
 }
 
-int fd_gemm_dw_batch(int n, const DwProb* probs, int K, const int* step, const float* hyper, int cfg,
-                     const FdAdamRest* rest, const FdLrSched* sched, float prox_mu, hipStream_t st) {
+int fd_gemm_dw_batch(int n, const DwProb* probs, int K, const int* step, const FdAdamHyper* h, int cfg,
+                     const FdAdamRest* rest, hipStream_t st) {
+  if (const int rc = h ? fd_adam_hyper_rc(h) : 0) return rc;
   if (n <= 0 || n > DWB_MAXP || K <= 0 || K % BKT) return 1;
-  // FedProx (adam_elem): a proximal term needs the fused Adam and an anchor beside every state it
-  // updates -- each problem's, and the arena's with the rest of the step (where a decaying sparse
-  // word table is refused: its rows without state drift from their anchors)
-  if (!(prox_mu >= 0.f) || !std::isfinite(prox_mu) || (prox_mu != 0.f && !hyper)) return 9;
-  if (prox_mu != 0.f) {
+  // FedProx (adam_elem): a proximal term comes with the fused Adam (h) and needs an anchor beside
+  // every state it updates -- each problem's, and the arena's with the rest of the step (where a
+  // decaying sparse word table is refused: its rows without state drift from their anchors)
+  if (h && h->mu != 0.f) {
     for (int i = 0; i < n; ++i)
       if (probs[i].p && !probs[i].anchor) return 9;
     if (rest && rest->p && (!rest->anchor || (rest->ever && rest->wwd != 0.f))) return 9;
   }
   DwBatch bt{};
-  bt.mu = prox_mu;
   if (rest && rest->p) {
-    if (!hyper || !step || !rest->g || !rest->m || !rest->v || (rest->nruns > 0) != (rest->runs != nullptr) ||
+    if (!h || !step || !rest->g || !rest->m || !rest->v || (rest->nruns > 0) != (rest->runs != nullptr) ||
         rest->n4 < 0 || (rest->ever && (rest->wrows <= 0 || rest->wrow4 <= 0 || rest->woff % 4)))
       return 7;
-    if ((rest->run_wd && !rest->runs) || (rest->ever && rest->wwd != 0.f && hyper[5] == 0.f)) return 8;
+    if ((rest->run_wd && !rest->runs) || (rest->ever && rest->wwd != 0.f && !h->decoupled)) return 8;
     bt.rest = *rest;
     // ~4 float4 per thread of the run table; one 64-row flag chunk per wave of the word table
     bt.rest.flat_blocks = rest->n4 > 0 ? (int)std::min<long long>(128, (rest->n4 + 2047) / 2048) : 0;
@@ -2746,13 +2737,11 @@ int fd_gemm_dw_batch(int n, const DwProb* probs, int K, const int* step, const f
     bt.pr[i] = probs[i];
     if (!probs[i].A || !probs[i].B || (!probs[i].C && !probs[i].p) || probs[i].M <= 0 || probs[i].N <= 0) return 2;
     if (probs[i].K < 0 || probs[i].K % BKT) return 5;
-    if (probs[i].p && (!probs[i].m || !probs[i].v || !step || !hyper)) return 3;
+    if (probs[i].p && (!probs[i].m || !probs[i].v || !step || !h)) return 3;
   }
-  if (hyper) {
+  if (h) {
     bt.step = step;
-    bt.lr = hyper[0]; bt.b1 = hyper[1]; bt.b2 = hyper[2]; bt.eps = hyper[3]; bt.wd = hyper[4];
-    bt.decoupled = hyper[5] != 0.f;
-    if (sched) bt.sched = *sched;  // (hyper[0]: its base rate)
+    bt.h = *h;
   }
   int id = cfg;
   if (id < 0) {

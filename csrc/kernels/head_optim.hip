@@ -176,9 +176,8 @@ __global__ __launch_bounds__(256) void eval_metrics_kernel(const float* logits, 
 
 template <bool NT, bool NTP = false>
 __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a) {
-  float lr_t, step_size, inv_sqrt_bc2;
-  adam_bias_corr(a.step, a.lr, a.sched, a.b1, a.b2, lr_t, step_size, inv_sqrt_bc2);
-  a.lr = lr_t;
+  float step_size, inv_sqrt_bc2;
+  adam_bias_corr(a.step, a.h, step_size, inv_sqrt_bc2);
   for (long long vi = blockIdx.x * 256ll + threadIdx.x; vi < a.n4; vi += (long long)gridDim.x * 256)
     adam_flat4<NT, NTP>(a, vi, step_size, inv_sqrt_bc2);
 }
@@ -193,9 +192,8 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a) {
 __global__ __launch_bounds__(256) void adam_rows_kernel(AdamArgs a, int rows, int row4) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= rows || !a.touched[row]) return;  // wave-uniform
-  float lr_t, step_size, inv_sqrt_bc2;
-  adam_bias_corr(a.step, a.lr, a.sched, a.b1, a.b2, lr_t, step_size, inv_sqrt_bc2);
-  a.lr = lr_t;
+  float step_size, inv_sqrt_bc2;
+  adam_bias_corr(a.step, a.h, step_size, inv_sqrt_bc2);
   if (row4 == 192) adam_row768(a, row, lane, step_size, inv_sqrt_bc2);
   else adam_row(a, 0, row, row4, lane, step_size, inv_sqrt_bc2);
 }
@@ -215,8 +213,7 @@ struct LazyDecayArgs {
   const unsigned char* ever;
   const int* step;
   int adj;
-  float lr, wd;
-  FdLrSched sched;  // lr is its base rate
+  FdAdamHyper h;    // (lr, wd and sched are read: each missed step's rate, one after another)
   int rows, row4;
   const void* ids;  // nullable
   int ids64;
@@ -239,11 +236,11 @@ __global__ __launch_bounds__(256) void adam_lazy_decay_kernel(LazyDecayArgs a) {
     const long long i = row * a.row4 + c;
     float4 p = reinterpret_cast<const float4*>(a.p)[i];
     for (int s = old + 1; s <= target; ++s) {
-      const float lr_s = adam_lr_at(a.lr, a.sched, s);
-      adam_decay(lr_s, a.wd, p.x);
-      adam_decay(lr_s, a.wd, p.y);
-      adam_decay(lr_s, a.wd, p.z);
-      adam_decay(lr_s, a.wd, p.w);
+      const float lr_s = adam_lr_at(a.h.lr, a.h.sched, s);
+      adam_decay(lr_s, a.h.wd, p.x);
+      adam_decay(lr_s, a.h.wd, p.y);
+      adam_decay(lr_s, a.h.wd, p.z);
+      adam_decay(lr_s, a.h.wd, p.w);
     }
     reinterpret_cast<float4*>(a.p)[i] = p;
     if (a.shadow) reinterpret_cast<uint2*>(a.shadow)[i] = make_uint2(pack_bf2(p.x, p.y), pack_bf2(p.z, p.w));
@@ -441,25 +438,26 @@ int fd_eval_metrics(const float* logits, const long long* labels, int B, double*
   return 0;
 }
 
-int fd_adam(float* p, const float* g, float* m, float* v, void* shadow, long long n, const int* step, float lr,
-            float b1, float b2, float eps, float wd, int decoupled, const unsigned char* touched,
-            const unsigned char* now, long long skip_off, long long skip_rows, int row_len, const long long* runs,
-            int nruns, long long run_total4, const float* run_wd, const FdLrSched* sched, float prox_mu,
-            const float* anchor, hipStream_t st) {
+// h: the step's hyper-parameters (adam_epi.h FdAdamHyper), checked first in every launcher below
+int fd_adam(float* p, const float* g, float* m, float* v, void* shadow, long long n, const int* step,
+            const FdAdamHyper* h, const unsigned char* touched, const unsigned char* now, long long skip_off,
+            long long skip_rows, int row_len, const long long* runs, int nruns, long long run_total4,
+            const float* run_wd, const float* anchor, hipStream_t st) {
+  if (const int rc = fd_adam_hyper_rc(h)) return rc;
   if (n % 4 != 0 || skip_off % 4 != 0 || row_len % 4 != 0) return 1;
   // FedProx (adam_elem): anchor is laid out like p.  Skipping untouched rows stays exact under it
   // without weight decay: such a row equals its anchor, so its proximal gradient is mu * (+0).
-  if (!(prox_mu >= 0.f) || !std::isfinite(prox_mu) || (prox_mu != 0.f && !anchor)) return 6;
+  if (h->mu != 0.f && !anchor) return 6;
   // skipping untouched rows is exact without weight decay; with decoupled decay the caller owes
   // those rows their multiplications (fd_adam_lazy_decay)
-  if (wd != 0.f && touched && !decoupled) return 3;
+  if (h->wd != 0.f && touched && !h->decoupled) return 3;
   // (a decaying row without state drifts from its anchor: nothing can be skipped then)
-  if (prox_mu != 0.f && wd != 0.f && touched) return 7;
+  if (h->mu != 0.f && h->wd != 0.f && touched) return 7;
   if (run_wd && (touched || !runs)) return 5;
   if (runs && (nruns <= 0 || run_total4 <= 0)) return 4;
-  AdamArgs a{p, g, m, v, (bf16_t*)shadow, runs ? run_total4 : n / 4, step, lr, b1, b2, eps, wd, decoupled,
+  AdamArgs a{p, g, m, v, (bf16_t*)shadow, runs ? run_total4 : n / 4, step, *h,
              skip_off / 4, (skip_off + skip_rows * row_len) / 4, row_len / 4, touched, now, runs, nruns, run_wd,
-             anchor, prox_mu, sched ? *sched : FdLrSched{}};
+             anchor};
   const int grid = grid_for(n / 4);
   // FD_ADAM_NT: 0 = default cache policy, 1 = nontemporal g/m/v, 2 = also the fp32 master (default:
   // 2.336 vs 2.366-2.387 ms/step, profiles/r1_ab_adam_nt_master.txt -- only the bf16 shadow is re-read soon)
@@ -476,17 +474,16 @@ int fd_adam(float* p, const float* g, float* m, float* v, void* shadow, long lon
 // Adam over the flagged rows of a [rows][row_len] table (see adam_rows_kernel; wd != 0 only
 // decoupled: the unflagged rows' decay is applied lazily, fd_adam_lazy_decay).
 int fd_adam_rows(float* p, const float* g, float* m, float* v, void* shadow, int rows, int row_len, const int* step,
-                 float lr, float b1, float b2, float eps, const unsigned char* ever, const unsigned char* now,
-                 float wd, int decoupled, const FdLrSched* sched, float prox_mu, const float* anchor,
+                 const FdAdamHyper* h, const unsigned char* ever, const unsigned char* now, const float* anchor,
                  hipStream_t st) {
+  if (const int rc = fd_adam_hyper_rc(h)) return rc;
   if (row_len % 4 != 0 || rows <= 0 || !ever) return 1;
-  if (wd != 0.f && !decoupled) return 3;
+  if (h->wd != 0.f && !h->decoupled) return 3;
   // FedProx: anchor is the table's, laid out like p; exact while the table does not decay (a row
   // without state equals its anchor), refused when it does
-  if (!(prox_mu >= 0.f) || !std::isfinite(prox_mu) || (prox_mu != 0.f && !anchor)) return 6;
-  if (prox_mu != 0.f && wd != 0.f) return 7;
-  AdamArgs a{p, g, m, v, (bf16_t*)shadow, 0, step, lr, b1, b2, eps, wd, decoupled, 0, 0, row_len / 4, ever, now,
-             nullptr, 0, nullptr, anchor, prox_mu, sched ? *sched : FdLrSched{}};
+  if (h->mu != 0.f && !anchor) return 6;
+  if (h->mu != 0.f && h->wd != 0.f) return 7;
+  AdamArgs a{p, g, m, v, (bf16_t*)shadow, 0, step, *h, 0, 0, row_len / 4, ever, now, nullptr, 0, nullptr, anchor};
   hipLaunchKernelGGL(adam_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, a, rows, row_len / 4);  // wave per row
   return 0;
 }
@@ -494,12 +491,12 @@ int fd_adam_rows(float* p, const float* g, float* m, float* v, void* shadow, int
 // The decoupled decay owed to the rows of a [rows][row_len] table without Adam state
 // (adam_lazy_decay_kernel): the rows named by the n entries of ids, or every row (ids == nullptr).
 int fd_adam_lazy_decay(float* p, void* shadow, int* done, const unsigned char* ever, int rows, int row_len,
-                       const int* step, int adj, float lr, float wd, const void* ids, int ids64, long long n,
-                       const FdLrSched* sched, hipStream_t st) {
+                       const int* step, int adj, const FdAdamHyper* h, const void* ids, int ids64, long long n,
+                       hipStream_t st) {
+  if (const int rc = fd_adam_hyper_rc(h)) return rc;
   if (row_len % 4 != 0 || rows <= 0 || !p || !done || !ever || !step || adj < 0) return 1;
   if (ids && (n <= 0 || n > (1ll << 30))) return 2;
-  LazyDecayArgs a{p, (bf16_t*)shadow, done, ever, step, adj, lr, wd, sched ? *sched : FdLrSched{}, rows, row_len / 4,
-                  ids, ids64, ids ? (int)n : rows};
+  LazyDecayArgs a{p, (bf16_t*)shadow, done, ever, step, adj, *h, rows, row_len / 4, ids, ids64, ids ? (int)n : rows};
   hipLaunchKernelGGL(adam_lazy_decay_kernel, dim3((a.n + 3) / 4), dim3(256), 0, st, a);
   return 0;
 }

@@ -400,21 +400,24 @@ class ArenaAdam:
             return None
         return (self.prox_mu, self.anchor if sl is None else self.anchor[sl])
 
+    def _hyper(self, wd: float, sl: Optional[slice] = None):
+        """This step's hyper-parameters as ``K.adam`` / ``K.adam_rows`` take them, spelled once: the
+        positional (lr, b1, b2, eps) and the keywords wd / decoupled / sched / prox, for weight decay
+        ``wd`` and the anchor of the whole arena or of its elements ``sl``."""
+        b1, b2 = self.betas
+        return ((self.lr, b1, b2, self.eps),
+                dict(wd=wd, decoupled=self.decoupled, sched=self.sched_args(), prox=self.prox_args(sl)))
+
     def _update(self, off: int, n: int, sparse: bool):
         from ..ops import kernels as K
         A = self.arena
-        b1, b2 = self.betas
         sl = slice(off, off + n)
-        wd = self._span_decay(off, n) if self.grouped_decay else self.weight_decay
-        prox = self.prox_args(sl)
+        hp, kw = self._hyper(self._span_decay(off, n) if self.grouped_decay else self.weight_decay, sl)
         if sparse:
             woff, rows, rl = self.model.word_embedding_span()
-            K.adam(A.master[sl], A.grad[sl], self.m[sl], self.v[sl], A.shadow[sl], self.step_t, self.lr, b1, b2,
-                   self.eps, wd, self.decoupled, self.model.emb_ever, self.model.emb_now, woff - off,
-                   rows, rl, sched=self.sched_args(), prox=prox)
-        else:
-            K.adam(A.master[sl], A.grad[sl], self.m[sl], self.v[sl], A.shadow[sl], self.step_t, self.lr, b1, b2,
-                   self.eps, wd, self.decoupled, sched=self.sched_args(), prox=prox)
+            kw.update(touched=self.model.emb_ever, now=self.model.emb_now, skip_off=woff - off, skip_rows=rows,
+                      row_len=rl)
+        K.adam(A.master[sl], A.grad[sl], self.m[sl], self.v[sl], A.shadow[sl], self.step_t, *hp, **kw)
 
     def _on_layer_grads(self, i: int):
         """Backward hook: block i's gradients are final -> update it on the side stream."""
@@ -460,10 +463,9 @@ class ArenaAdam:
             st += [A.master[off:off + n], self.m[off:off + n], self.v[off:off + n], A.shadow[off:off + n]]
             self._done.append((off, n))
         st.append(self.step_t)
-        b1, b2 = self.betas
-        hp = FusedHyper([self.lr, b1, b2, self.eps, self.weight_decay, 1.0 if self.decoupled else 0.0])
-        hp.sched = self.sched_args()
-        hp.prox = self.prox_args()
+        pos, kw = self._hyper(self.weight_decay)
+        hp = FusedHyper([*pos, kw["wd"], 1.0 if kw["decoupled"] else 0.0])
+        hp.sched, hp.prox = kw["sched"], kw["prox"]
         return st, hp
 
     def _runs_table(self, runs):
@@ -610,7 +612,7 @@ class ArenaAdam:
         if A.master.device != self.m.device:
             self._alloc()
         b1, b2 = self.betas
-        sc = self.sched_args()  # (raises while a schedule's total is unresolved)
+        self.sched_args()  # (raises while a schedule's total is unresolved)
         if A.master.is_cuda:
             self._begin()
             if getattr(self, "_rest_in_launch", False):
@@ -634,23 +636,22 @@ class ArenaAdam:
                 _, rows, rl = self.model.word_embedding_span()
                 wend = woff + rows * rl
                 sl = slice(woff, wend)
-                K.adam_rows(A.master[sl], A.grad[sl], self.m[sl], self.v[sl], A.shadow[sl], self.step_t, self.lr, b1,
-                            b2, self.eps, self.model.emb_ever, self.model.emb_now, rl, self.word_wd, self.decoupled,
-                            sched=sc, prox=self.prox_args(sl))
+                hp, kw = self._hyper(self.word_wd, sl)
+                K.adam_rows(A.master[sl], A.grad[sl], self.m[sl], self.v[sl], A.shadow[sl], self.step_t, *hp,
+                            self.model.emb_ever, self.model.emb_now, rl, **kw)
                 rest_table = self._runs_table(rest) if len(rest) > 1 else None
                 if rest_table is not None:
-                    K.adam(A.master, A.grad, self.m, self.v, A.shadow, self.step_t, self.lr, b1, b2, self.eps,
-                           self.weight_decay, self.decoupled, runs=rest_table, run_decay=self._runs_decay(rest),
-                           sched=sc, prox=self.prox_args())
+                    hp, kw = self._hyper(self.weight_decay)
+                    K.adam(A.master, A.grad, self.m, self.v, A.shadow, self.step_t, *hp, runs=rest_table,
+                           run_decay=self._runs_decay(rest), **kw)
                 else:
                     for off, n in rest:
                         self._update(off, n, False)
             elif table is not None:  # everything left (fused-GEMM spans excluded) in one launch
                 from ..ops import kernels as K
-                b1, b2 = self.betas
-                K.adam(A.master, A.grad, self.m, self.v, A.shadow, self.step_t, self.lr, b1, b2, self.eps,
-                       self.weight_decay, self.decoupled, runs=table, run_decay=self._runs_decay(runs), sched=sc,
-                       prox=self.prox_args())
+                hp, kw = self._hyper(self.weight_decay)
+                K.adam(A.master, A.grad, self.m, self.v, A.shadow, self.step_t, *hp, runs=table,
+                       run_decay=self._runs_decay(runs), **kw)
             else:
                 for off, n in runs:
                     self._update(off, n, sparse and off <= woff < off + n)

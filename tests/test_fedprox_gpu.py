@@ -303,6 +303,26 @@ def test_prox_with_decaying_word_table_trains_dense(nosplit):
     assert not torch.equal(fused[1], _unfused_ref()[1])
 
 
+def test_schedule_prox_and_parameter_groups_in_one_step(nosplit):
+    """A linear schedule (2 warmup steps of 8), a proximal term and AdamW parameter groups in the
+    same 5 steps -- the three travel in one hyper-parameter descriptor (csrc/kernels/adam_epi.h
+    FdAdamHyper).  The word table is in the no-decay group, so the sparse word path and the rest of
+    the step stay inside the dW launch.  Fused eager, fused graphed and unfused eager agree bitwise
+    (losses, master, m, v, shadow; _train asserts can_fuse() for the fused arms), and the result
+    is not that of the same run with prox_mu = 0."""
+    kw = dict(schedule="linear", warmup_steps=2, total_steps=8, weight_decay=WD, decoupled=True,
+              no_decay=HF_NO_DECAY + ("word_embeddings",))
+    unfused, fused, graphed = _train(False, False, **kw), _train(True, False, **kw), _train(True, True, **kw)
+    for arm in (fused, graphed):
+        assert arm[6].can_fuse() and arm[6].word_wd == 0.0 and arm[6].grouped_decay
+        assert arm[5].sparse_word_grad and arm[6].sched_args() == (1, 2, 8, 0)
+    assert graphed[7].graph is not None and graphed[7].failed is None
+    _same(fused, unfused)
+    _same(graphed, unfused)
+    plain = _train(True, False, mu=0.0, **kw)
+    assert not torch.equal(plain[1], fused[1])
+
+
 def test_prox_anchor_resnapshot_is_what_graph_replays_read(nosplit):
     """Capture, train 3 steps, reset_state(), train 3 more through the same captured graphs (two
     batches in turn, so every step after the reset finds its graph: no new capture): bitwise the
