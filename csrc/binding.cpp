@@ -149,6 +149,9 @@ int fd_axpby(float* dst, const float* x, const float* y, float a, float b, long 
 int fd_server_opt_grid(long long n);
 int fd_server_opt(float* master, float* x, float* m, float* v, void* shadow, long long n, int kind, float inv,
                   float eta, float b1, float b2, float tau, float* stats, hipStream_t st);
+int fd_robust_agg_grid(long long n);
+int fd_robust_agg(const float* const* src, int M, int k, float* out, void* shadow, int* counts, long long n,
+                  hipStream_t st);
 }
 
 namespace {
@@ -1826,6 +1829,49 @@ void server_opt(const at::Tensor& master, const at::Tensor& x, const at::Tensor&
 // Blocks of a server_opt launch over n floats (the stats buffer holds two floats per block).
 int64_t server_opt_grid(int64_t n) { return (int64_t)fd_server_opt_grid(n); }
 
+// Byzantine-robust aggregation (robust_agg.hip): out = the coordinate-wise trimmed mean of the M
+// sources with the k lowest and k highest values dropped (k = (M - 1) / 2: the median), shadow
+// (optional) = bf16(out), counts (optional, int32, >= 17 * grid) = per block the trimmed count of
+// each slot (columns 0..15) and the non-finite outputs (column 16).  Nothing is launched unless
+// every check passes; out and shadow must not overlap a source.
+void robust_agg(const std::vector<at::Tensor>& srcs, int64_t k, const at::Tensor& out,
+                const c10::optional<at::Tensor>& shadow, const c10::optional<at::Tensor>& counts) {
+  const int64_t M = (int64_t)srcs.size();
+  TORCH_CHECK(M >= 2 && M <= 16, "robust_agg: 2 <= M <= 16 sources, got ", M);
+  TORCH_CHECK(k >= 0 && 2 * k < M, "robust_agg: 0 <= 2k < M, got k = ", k, " with M = ", M);
+  need(out, at::kFloat, "out");
+  need_opt(shadow, at::kBFloat16, "shadow");
+  need_opt(counts, at::kInt, "counts");
+  const bool has_shadow = shadow.has_value() && shadow->defined();
+  const bool has_counts = counts.has_value() && counts->defined();
+  const int64_t n = out.numel();
+  TORCH_CHECK(n > 0 && n % 4 == 0, "robust_agg: numel % 4");
+  const auto dev = out.device();
+  TORCH_CHECK((!has_shadow || shadow->device() == dev) && (!has_counts || counts->device() == dev),
+              "robust_agg: tensors on one device");
+  if (has_shadow) TORCH_CHECK(shadow->numel() == n, "robust_agg: shadow size");
+  if (has_counts) TORCH_CHECK(counts->numel() >= 17 * (int64_t)fd_robust_agg_grid(n), "robust_agg: counts size");
+  const auto overlaps = [](const void* a, int64_t abytes, const void* b, int64_t bbytes) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + (uintptr_t)bbytes && b0 < a0 + (uintptr_t)abytes;
+  };
+  const float* ptrs[16];
+  for (int64_t s = 0; s < M; ++s) {
+    need(srcs[s], at::kFloat, "source");
+    TORCH_CHECK(srcs[s].device() == dev, "robust_agg: tensors on one device");
+    TORCH_CHECK(srcs[s].numel() == n, "robust_agg: source ", s, " has ", srcs[s].numel(), " elements, out ", n);
+    ptrs[s] = srcs[s].data_ptr<float>();
+    TORCH_CHECK(!overlaps(ptrs[s], n * 4, out.data_ptr(), n * 4), "robust_agg: out overlaps source ", s);
+    if (has_shadow)
+      TORCH_CHECK(!overlaps(ptrs[s], n * 4, shadow->data_ptr(), n * 2), "robust_agg: shadow overlaps source ", s);
+  }
+  check_rc(fd_robust_agg(ptrs, (int)M, (int)k, out.data_ptr<float>(), ptr<void>(shadow), ptr<int>(counts), n, stream()),
+           "robust_agg");
+}
+
+// Blocks of a robust_agg launch over n floats (the counts buffer holds 17 ints per block).
+int64_t robust_agg_grid(int64_t n) { return (int64_t)fd_robust_agg_grid(n); }
+
 }  // namespace
 
 #ifndef FD_HOST_VALIDATION
@@ -1945,5 +1991,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("kind"), py::arg("inv"), py::arg("eta"), py::arg("b1"), py::arg("b2"), py::arg("tau"),
         py::arg("stats") = py::none());
   m.def("server_opt_grid", &server_opt_grid);
+  m.def("robust_agg", &robust_agg, py::arg("srcs"), py::arg("k"), py::arg("out"), py::arg("shadow") = py::none(),
+        py::arg("counts") = py::none());
+  m.def("robust_agg_grid", &robust_agg_grid);
 }
 #endif  // FD_HOST_VALIDATION

@@ -677,6 +677,38 @@ int fd_server_opt(float* master, float* x, float* m, float* v, void* shadow, lon
     hc::violations.push_back("server_opt: hyper-parameters out of range");
   return 0;
 }
+// (the grid of fd_server_opt -- csrc/kernels/robust_agg.hip ra_grid_for)
+int fd_robust_agg_grid(long long n) { return fd_server_opt_grid(n); }
+int fd_robust_agg(const float* const* src, int M, int k, float* out, void* shadow, int* counts, long long n,
+                  hipStream_t) {
+  ++hc::calls;
+  // the kernel reads n / 4 float4 of each of the M sources, writes as many to out (and uint2 to the
+  // shadow), and 17 ints per block of counts
+  if (n <= 0 || n % 4 != 0) hc::violations.push_back("robust_agg: n % 4");
+  if (M < 2 || M > 16) {
+    hc::violations.push_back("robust_agg: M");
+    return 0;
+  }
+  if (k < 0 || 2 * k >= M) hc::violations.push_back("robust_agg: k");
+  hc::span(out, n * 4, "robust_agg out");
+  hc::opt_span(shadow, n * 2, "robust_agg shadow");
+  hc::opt_span(counts, 17LL * fd_robust_agg_grid(n) * 4, "robust_agg counts");
+  if (!src) {
+    hc::violations.push_back("robust_agg: no sources");
+    return 0;
+  }
+  const auto overlaps = [](const void* a, long long ab, const void* b, long long bb) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + (uintptr_t)bb && b0 < a0 + (uintptr_t)ab;
+  };
+  for (int s = 0; s < M; ++s) {
+    hc::span(src[s], n * 4, "robust_agg source");
+    if (src[s] && overlaps(src[s], n * 4, out, n * 4)) hc::violations.push_back("robust_agg: out overlaps a source");
+    if (src[s] && shadow && overlaps(src[s], n * 4, shadow, n * 2))
+      hc::violations.push_back("robust_agg: shadow overlaps a source");
+  }
+  return 0;
+}
 }  // extern "C"
 
 // ------------------------------------------------------------------ driver
@@ -1263,6 +1295,56 @@ int main() {
     expect_reject("server_opt b1 = 1", [&] { server_opt(ms, x, m, v, sh, 2, 0.5, 1e-2, 1.0, 0.99, 1e-3, st); });
     expect_reject("server_opt b2 < 0", [&] { server_opt(ms, x, m, v, sh, 2, 0.5, 1e-2, 0.9, -0.1, 1e-3, st); });
     expect_reject("server_opt inv inf", [&] { server_opt(ms, x, m, v, sh, 2, inf, 1e-2, 0.9, 0.99, 1e-3, st); });
+  }
+  // ---- robust aggregation: M fp32 sources, out, the bf16 shadow, 17 count ints per block
+  {
+    const int64_t n = 4096 * 1024 + 4 * 257;  // the grid-stride loop wraps, ragged last block
+    const int64_t nc = 17 * fd_robust_agg_grid(n);
+    std::vector<at::Tensor> s3, s16, s17;
+    for (int i = 0; i < 17; ++i) {
+      auto t = T_({n}, f32);
+      if (i < 3) s3.push_back(t);
+      if (i < 16) s16.push_back(t);
+      s17.push_back(t);
+    }
+    auto out = T_({n}, f32), sh = T_({n}, bf), ct = T_({nc}, i32);
+    expect_ok("robust_agg M 3 median", [&] { robust_agg(s3, 1, out, sh, ct); });
+    expect_ok("robust_agg M 3 mean, no shadow / counts", [&] { robust_agg(s3, 0, out, none, none); });
+    expect_ok("robust_agg M 16 median", [&] { robust_agg(s16, 7, out, sh, ct); });
+    expect_ok("robust_agg M 2", [&] { robust_agg({s3[0], s3[1]}, 0, out, sh, none); });
+    std::vector<at::Tensor> sm;
+    for (int i = 0; i < 5; ++i) sm.push_back(T_({2048}, f32));
+    auto o8 = T_({2048}, f32), c8 = T_({17 * 2}, i32);
+    expect_ok("robust_agg small", [&] { robust_agg(sm, 2, o8, none, c8); });
+    expect_reject("robust_agg M 1", [&] { robust_agg({s3[0]}, 0, out, sh, ct); });
+    expect_reject("robust_agg M 17", [&] { robust_agg(s17, 1, out, sh, ct); });
+    expect_reject("robust_agg 2k = M", [&] { robust_agg(s16, 8, out, sh, ct); });
+    expect_reject("robust_agg 2k > M", [&] { robust_agg(s3, 2, out, sh, ct); });
+    expect_reject("robust_agg k < 0", [&] { robust_agg(s3, -1, out, sh, ct); });
+    auto srt = T_({n - 4}, f32), shs = T_({n - 4}, bf), ct_short = T_({nc - 1}, i32);
+    expect_reject("robust_agg short source", [&] { robust_agg({s3[0], srt, s3[2]}, 1, out, sh, ct); });
+    expect_reject("robust_agg short out", [&] { robust_agg(s3, 1, srt, none, ct); });
+    expect_reject("robust_agg short shadow", [&] { robust_agg(s3, 1, out, shs, ct); });
+    expect_reject("robust_agg short counts", [&] { robust_agg(s3, 1, out, sh, ct_short); });
+    auto sb = T_({n}, bf), shf = T_({n}, f32), ctf = T_({nc}, f32), ob = T_({n}, bf);
+    expect_reject("robust_agg source dtype", [&] { robust_agg({s3[0], sb, s3[2]}, 1, out, sh, ct); });
+    expect_reject("robust_agg out dtype", [&] { robust_agg(s3, 1, ob, sh, ct); });
+    expect_reject("robust_agg shadow dtype", [&] { robust_agg(s3, 1, out, shf, ct); });
+    expect_reject("robust_agg counts dtype", [&] { robust_agg(s3, 1, out, sh, ctf); });
+    auto xt = T_({2, n / 2}, f32).t();
+    expect_reject("robust_agg non-contiguous source", [&] { robust_agg({s3[0], s3[1], xt}, 1, out, sh, ct); });
+    std::vector<at::Tensor> s6;
+    for (int i = 0; i < 3; ++i) s6.push_back(T_({2046}, f32));
+    auto o6 = T_({2046}, f32);
+    expect_reject("robust_agg numel % 4", [&] { robust_agg(s6, 1, o6, none, none); });
+    expect_reject("robust_agg out is a source", [&] { robust_agg(s3, 1, s3[1], sh, ct); });
+    // out / shadow as a window of a source's allocation
+    auto big = T_({2 * n}, f32);
+    auto lo = big.narrow(0, 0, n), mid = big.narrow(0, n / 2, n), hi = big.narrow(0, n, n);
+    expect_reject("robust_agg out overlaps a source", [&] { robust_agg({s3[0], lo, s3[2]}, 1, mid, sh, ct); });
+    expect_ok("robust_agg out beside a source", [&] { robust_agg({s3[0], lo, s3[2]}, 1, hi, sh, ct); });
+    auto shv = big.narrow(0, n / 2, n / 2).view(bf);
+    expect_reject("robust_agg shadow overlaps a source", [&] { robust_agg({s3[0], lo, s3[2]}, 1, out, shv, ct); });
   }
   // ---- embedding backward (work = pieces + LayerNorm partials)
   {

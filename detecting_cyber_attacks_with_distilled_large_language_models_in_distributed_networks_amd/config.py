@@ -17,6 +17,9 @@ from dataclasses import dataclass, field
 from typing import Optional
 
 
+_OPTIONAL_INTS = ("drop_client", "drop_round", "num_clients", "poison_client", "poison_round")
+
+
 @dataclass
 class FedConfig:
     # --- data (client1.py:23, :84-93, :356) -------------------------------------------
@@ -71,6 +74,11 @@ class FedConfig:
     server_lr: float = 1.0
     server_betas: tuple = (0.9, 0.99)
     server_tau: float = 1e-3                # adaptivity floor: v starts at tau^2
+    # Byzantine-robust aggregation (parallel/robust.py; Yin et al., ICML 2018): per coordinate the k
+    # lowest and k highest client values are dropped.  "mean": the plain mean (reference);
+    # "trimmed_mean": k = floor(trim_ratio * M) of the M participating clients; "median": k = (M - 1) // 2
+    aggregator: str = "mean"                # "mean" | "trimmed_mean" | "median"
+    trim_ratio: float = 0.2                 # trimmed_mean: share trimmed at each end, in [0, 0.5)
     participation: float = 1.0              # fraction of clients aggregated per round
     timeout_s: float = 300.0                # server.py:10 / client1.py:22
     heartbeat_s: float = 1.0                # failure detection (parallel/health.py); 0 disables
@@ -91,6 +99,11 @@ class FedConfig:
     # --- fault injection -------------------------------------------------
     drop_client: Optional[int] = None       # client whose update is dropped ...
     drop_round: Optional[int] = None        # ... at this round
+    # a client that lies (utils/faults.py poison_): its master is replaced just before the exchange
+    poison_client: Optional[int] = None     # the client that lies ...
+    poison_round: Optional[int] = None      # ... at this round (None: every round)
+    poison_kind: str = "scale"              # "scale" (master *= poison_scale) | "noise" | "nan"
+    poison_scale: float = -4.0              # scale: the factor; noise: sigma = |poison_scale|
     # --- distillation extension (BASELINE.json config 5) ------------------------------
     teacher: Optional[str] = None           # "bert-base" -> KD from a 12-layer teacher
     kd_temperature: float = 2.0
@@ -128,7 +141,7 @@ class FedConfig:
                 parser.add_argument(name, dest=f.name, default=None, type=float, nargs=len(default))
             else:
                 typ = type(default) if default is not None else str
-                if f.name in ("drop_client", "drop_round", "num_clients"):
+                if f.name in _OPTIONAL_INTS:
                     typ = int
                 parser.add_argument(name, dest=f.name, default=None, type=typ)
         return parser
@@ -152,6 +165,6 @@ def _coerce(f, raw: str, current):
         return float(raw)
     if isinstance(current, tuple):
         return tuple(float(x) for x in raw.split(","))
-    if current is None and f.name in ("drop_client", "drop_round", "num_clients"):
+    if current is None and f.name in _OPTIONAL_INTS:
         return int(raw)
     return raw

@@ -30,6 +30,7 @@ from ..models import DDoSClassifier, DistilBertConfig
 from ..parallel import comm, health
 from ..parallel.dp import DPShardLoader, GradSync, dp_seed_offset, make_topology
 from ..parallel.fedavg import broadcast_model, fedavg_
+from ..parallel.robust import check_robust_config, make_robust, most_trimmed, robust_aggregate_
 from ..parallel.server_opt import check_server_config, make_server_optimizer
 from ..utils import checkpoint as ck
 from ..utils import faults
@@ -107,6 +108,7 @@ class FederatedClient:
     def setup(self):
         cfg, log = self.cfg, self.log
         check_server_config(cfg)  # (an unknown kind, a bad value, or transport=tcp: refused before any work)
+        check_robust_config(cfg)  # (likewise: an unknown aggregator, tcp, weighted_fedavg)
         log.phase("Starting client")
         with self.timer("preprocess"):
             if self.frame is None:
@@ -177,6 +179,11 @@ class FederatedClient:
                      f"({self.server.b1:g}, {self.server.b2:g}), tau {self.server.tau:g})")
             if self.start_round > 0:
                 self._resume_server()
+        # Byzantine-robust aggregator (parallel/robust.py; None: the plain mean, today's path)
+        self.robust = make_robust(cfg, self.topo.gpus_per_client)
+        if self.robust is not None:
+            log.info(f"robust aggregation: {self.robust.aggregator}"
+                     + (f" (trim_ratio {self.robust.trim_ratio:g})" if self.robust.aggregator == "trimmed_mean" else ""))
         self.health = None
         if self.di.distributed and cfg.heartbeat_s > 0 and cfg.transport != "tcp":
             self.health = health.start(cfg.heartbeat_s, cfg.heartbeat_stale_s, cfg.timeout_s)
@@ -318,6 +325,8 @@ class FederatedClient:
             except health.PeerFailure as e:
                 log.info(f"[ERROR] {e}; aborting round {r + 1} (restart resumes from the last completed round)")
                 raise
+        if faults.poison_(model.arena.master, cfg, self.idx, r):  # (this client lies: utils/faults.py)
+            log.info(f"[FAULT] sending a poisoned update ({cfg.poison_kind})")
         with self.timer("fedavg"):
             t0 = time.perf_counter()
             if cfg.transport == "tcp":
@@ -326,6 +335,9 @@ class FederatedClient:
                 total_w = self._tcp_exchange(contributes) if self.topo.dp_rank == 0 else 0.0
                 if self.topo.dp:
                     total_w = self._dp_share_model(total_w)
+            elif self.robust is not None:
+                total_w = fedavg_(model, participate=contributes, comm=self.comm, server=self.server,
+                                  robust=self.robust)
             else:
                 total_w = fedavg_(model, weight=weight, participate=contributes, comm=self.comm, server=self.server)
             if model.device.type == "cuda":
@@ -337,6 +349,9 @@ class FederatedClient:
         if norms is not None:
             log.info(f"server {self.server.kind} step: |avg - global| = {norms['delta_l2']:.6g}, "
                      f"|step| = {norms['step_l2']:.6g}")
+        trim = self.robust.last if self.robust is not None and total_w > 0 else None
+        if trim is not None:
+            log.info(_trim_line(trim))
         if self.di.is_main and cfg.save_checkpoints:
             # weights, the server optimizer's moments, then the round tag (_resume)
             ck.save_global(model, cfg.out_dir, r + 1, server=self.server)
@@ -363,6 +378,8 @@ class FederatedClient:
             rec["teacher_test"] = teacher_test
         if norms is not None:
             rec.update(delta_l2=norms["delta_l2"], step_l2=norms["step_l2"])
+        if trim is not None:
+            rec.update(trimmed_share=trim["trimmed_share"], k=trim["k"])
         self.history.append(rec)
         if self.writer:
             ck.save_fed_state(cfg.out_dir, self.client_id, {"completed_rounds": r + 1, "history": self.history})
@@ -430,6 +447,14 @@ class FederatedClient:
                 json.dump(rep, f, indent=1)
             self.log.info(f"federated report written to {path}")
         return rep
+
+
+def _trim_line(trim: Dict) -> str:
+    """One log line for a robust round: the most-trimmed slot (the j-th participating client, in
+    client order) and its share; honest i.i.d. clients sit near 2k / M each."""
+    j, share = most_trimmed(trim)
+    return (f"robust aggregate of {trim['clients']} client(s), k = {trim['k']}: most trimmed is participant "
+            f"{j + 1} with share {share:.4f} (honest expectation {2 * trim['k'] / max(trim['clients'], 1):.4f})")
 
 
 @torch.no_grad()
@@ -512,6 +537,12 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
     scale, and each round's record carries its ``delta_l2`` / ``step_l2``
     (tests/test_server_opt_cpu.py: equal to the 2-rank gloo run bit for bit).
 
+    With a robust aggregator (``cfg.aggregator``, parallel/robust.py) ``robust_aggregate_`` takes the
+    place of ``_average_masters`` -- the call ``fedavg_(..., robust=)`` makes on the gathered rows -- and
+    each round's record carries ``trimmed_share`` / ``k`` (tests/test_robust_agg_cpu.py: equal to the
+    3-rank gloo run bit for bit).  A poisoned client (``cfg.poison_client``, utils/faults.py) sends a
+    changed copy of its weights; its local metrics are those of the weights it trained.
+
     Returns ``rounds`` (one record per round: per-client local / aggregated metrics, the pooled
     aggregated confusion, the FedAvg time) plus the LAST round's ``clients`` /
     ``aggregated_confusion`` / ``fedavg_ms`` at the top level (the 1-round API of earlier rounds).
@@ -535,6 +566,7 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
         # global model by definition, and moments of other weights mean nothing
         client.log.info("[WARN] the model changed since the server optimizer was built: server state reset")
         server.reset(model)
+    robust = make_robust(cfg)  # (None: the plain mean -- _average_masters, untouched)
     t_init = teacher.arena.master.detach().clone() if teacher is not None else None
     say = progress or (lambda msg: None)
     # per-client state that survives the rounds (a real client's process keeps it)
@@ -588,6 +620,7 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
             c["torch_counter"] = model.torch_counter
             local = _metrics_record(evaluate_model(model, test, name=f"Client {v + 1} local test"))
             locals_.append(A.master.detach().clone())
+            faults.poison_(locals_[-1], cfg, v, r)  # (a lying client: what it sends, not what it evaluated)
             rec.update({"train": tr, "train_wall_s": time.perf_counter() - t0, "local_test": local})
             # client drift: how far the local epochs moved this client from the round's start
             rec["l2_local_to_start"] = float((locals_[-1] - glob).norm())
@@ -596,8 +629,11 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
             say(f"round {r + 1}/{rounds} client {v + 1}/{n_clients}: local acc {local['accuracy']:.3f} % "
                 f"f1 {local['f1']:.5f} ({tr['steps']} steps, {time.perf_counter() - t0:.1f} s)")
         t0 = time.perf_counter()
-        norms = None
-        if server is None:
+        norms = trim = None
+        if robust is not None:
+            trim = robust_aggregate_(model, locals_, robust.k(len(locals_)), server)
+            norms = server.last if server is not None else None
+        elif server is None:
             _average_masters(model, locals_)
         else:
             norms = _average_masters(model, locals_, server)
@@ -616,6 +652,10 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
                      "local_confusion": _pooled(recs, "local_test")})
         if norms is not None:  # the server step: how far the average drifted, how far the server moved
             hist[-1].update(delta_l2=norms["delta_l2"], step_l2=norms["step_l2"])
+        if trim is not None:  # how often each client's value was the one trimmed (parallel/robust.py)
+            hist[-1].update(trimmed_share=trim["trimmed_share"], k=trim["k"])
+            client.log.info(_trim_line(trim))
+            say(f"round {r + 1}/{rounds} " + _trim_line(trim))
         (tn, fp), (fn, tp) = pooled
         say(f"round {r + 1}/{rounds} aggregate: pooled acc {100.0 * (tp + tn) / max(tp + tn + fp + fn, 1):.3f} %")
     last = hist[-1]

@@ -1147,3 +1147,23 @@ def server_opt(master, x, m, v, shadow, kind, inv, eta, b1, b2, tau, stats=None)
     if kind not in SERVER_OPT_KINDS:
         raise ValueError(f"server_opt: unknown kind {kind!r} (one of {sorted(SERVER_OPT_KINDS)})")
     ext().server_opt(master, x, m, v, shadow, SERVER_OPT_KINDS[kind], inv, eta, b1, b2, tau, stats)
+
+
+ROBUST_AGG_MAX_CLIENTS = 16
+ROBUST_AGG_COLS = 17  # a block's counts row: trimmed count of slots 0..15, then the non-finite outputs
+
+
+def robust_agg_grid(n):
+    """Blocks of a ``robust_agg`` launch over ``n`` floats (its ``counts`` holds 17 ints per block)."""
+    return int(ext().robust_agg_grid(int(n)))
+
+
+def robust_agg(srcs, k, out, shadow=None, counts=None):
+    """Coordinate-wise trimmed mean of the M = len(srcs) flat fp32 tensors in one pass (robust_agg.hip;
+    the specification is ``parallel.robust.torch_robust_``): per coordinate the k lowest and k highest
+    values are dropped (k = (M - 1) // 2: the median), the rest summed ascending and scaled by
+    1 / (M - 2k) into ``out``; ``shadow`` = bf16(out).  2 <= M <= 16, 0 <= 2k < M; ``out`` / ``shadow``
+    must not overlap a source.  ``counts`` (int32, >= 17 * ``robust_agg_grid(n)``): [block][17], per
+    block how often each slot's value was trimmed (columns >= M: 0) and, in column 16, the non-finite
+    outputs; every entry is written on every launch."""
+    ext().robust_agg(list(srcs), int(k), out, shadow, counts)

@@ -10,6 +10,10 @@ Knobs (config fields or env):
                               the dead rank within seconds.  One-shot per (k, r) when a
                               marker directory is given, so an elastic restart
                               (torchrun --max-restarts) of the same round succeeds.
+  poison_client / poison_round / poison_kind / poison_scale
+                              client k lies: just before the exchange its master is scaled by
+                              poison_scale ("scale"), gets N(0, poison_scale^2) noise ("noise") or
+                              becomes NaN ("nan"); poison_round None: every round
   participation < 1.0         seeded partial participation: each round a subset of
                               clients of size max(1, round(p*N)) contributes
 """
@@ -32,6 +36,38 @@ def participants(round_idx: int, num_clients: int, fraction: float, seed: int = 
 def dropped(cfg, client_idx: int, round_idx: int) -> bool:
     return cfg.drop_client is not None and cfg.drop_client == client_idx and \
         (cfg.drop_round is None or cfg.drop_round == round_idx)
+
+
+POISON_KINDS = ("scale", "noise", "nan")
+
+
+def poisoned(cfg, client_idx: int, round_idx: int) -> bool:
+    pc = getattr(cfg, "poison_client", None)
+    pr = getattr(cfg, "poison_round", None)
+    return pc is not None and pc == client_idx and (pr is None or pr == round_idx)
+
+
+def poison_(master, cfg, client_idx: int, round_idx: int) -> bool:
+    """Make client ``cfg.poison_client`` lie: its fp32 ``master`` (the update it is about to send) is
+    replaced in place -- "scale": ``master *= poison_scale``; "noise": ``master += |poison_scale| *
+    randn``, seeded from (base_seed, client, round); "nan": filled with NaN.  Called just before the
+    exchange, after the client's local metrics and checkpoint are written.  Returns whether it lied."""
+    if not poisoned(cfg, client_idx, round_idx):
+        return False
+    import torch
+    kind = str(cfg.poison_kind).lower()
+    with torch.no_grad():
+        if kind == "scale":
+            master.mul_(float(cfg.poison_scale))
+        elif kind == "noise":
+            g = torch.Generator().manual_seed((int(cfg.base_seed) * 1_000_003 + client_idx) * 1_000_003 + round_idx)
+            noise = torch.randn(master.numel(), generator=g, dtype=torch.float32)
+            master.add_(noise.to(master.device), alpha=abs(float(cfg.poison_scale)))
+        elif kind == "nan":
+            master.fill_(float("nan"))
+        else:
+            raise ValueError(f"poison_kind must be one of {', '.join(POISON_KINDS)}; got {cfg.poison_kind!r}")
+    return True
 
 
 def maybe_kill(client_idx: int, round_idx: int, marker_dir: Optional[str] = None, replica: int = 0,
