@@ -20,6 +20,7 @@ namespace py { struct gil_scoped_release {}; }  // (no Python in the host-only b
 
 #include <cmath>
 #include <cstdint>
+#include <limits>
 #include <vector>
 
 #include "kernels/adam_epi.h"
@@ -152,6 +153,14 @@ int fd_server_opt(float* master, float* x, float* m, float* v, void* shadow, lon
 int fd_robust_agg_grid(long long n);
 int fd_robust_agg(const float* const* src, int M, int k, float* out, void* shadow, int* counts, long long n,
                   hipStream_t st);
+int fd_privacy_grid(long long n);
+int fd_privacy_norm(const float* w, const float* anchor, double* partial, float* stats, float clip, long long n,
+                    hipStream_t st);
+int fd_privacy_apply(float* w, const float* anchor, void* shadow, const float* stats, float sigma, uint32_t seed_lo,
+                     uint32_t seed_hi, long long round, long long client, long long first4, long long n,
+                     hipStream_t st);
+int fd_privacy_gauss(float* out, uint32_t seed_lo, uint32_t seed_hi, long long round, long long client,
+                     long long first4, long long n, hipStream_t st);
 }
 
 namespace {
@@ -1872,6 +1881,96 @@ void robust_agg(const std::vector<at::Tensor>& srcs, int64_t k, const at::Tensor
 // Blocks of a robust_agg launch over n floats (the counts buffer holds 17 ints per block).
 int64_t robust_agg_grid(int64_t n) { return (int64_t)fd_robust_agg_grid(n); }
 
+// Client-level differential privacy (privacy.hip).  The stream of a call: the 64-bit seed as two
+// 32-bit words, the round and the client (one Philox counter word each), and first4, the float4 index
+// of the tensor's first element in that stream.
+void privacy_stream_check(int64_t seed_lo, int64_t seed_hi, int64_t round, int64_t client, int64_t first4, int64_t n,
+                          const char* what) {
+  const int64_t w32 = int64_t(1) << 32;
+  TORCH_CHECK(seed_lo >= 0 && seed_lo < w32 && seed_hi >= 0 && seed_hi < w32, what, ": seed words in [0, 2^32)");
+  TORCH_CHECK(round >= 0 && round < w32, what, ": round in [0, 2^32), got ", round);
+  TORCH_CHECK(client >= 0 && client < w32, what, ": client in [0, 2^32), got ", client);
+  TORCH_CHECK(first4 >= 0 && first4 <= std::numeric_limits<int64_t>::max() - n / 4, what, ": first4 >= 0, got ", first4);
+}
+
+bool privacy_overlap(const at::Tensor& a, const at::Tensor& b) {
+  const uintptr_t a0 = (uintptr_t)a.data_ptr(), b0 = (uintptr_t)b.data_ptr();
+  return a0 < b0 + (uintptr_t)(b.numel() * b.element_size()) && b0 < a0 + (uintptr_t)(a.numel() * a.element_size());
+}
+
+// Blocks of a privacy_norm / privacy_apply / privacy_gauss launch over n floats (partial holds one
+// double per block).
+int64_t privacy_grid(int64_t n) { return (int64_t)fd_privacy_grid(n); }
+
+// stats[4] = {|w - anchor|_2, scale, flag, 0}: flag 0 / scale 1 when the norm is <= clip, flag 1 /
+// scale clip / norm above it, flag 2 / scale 0 when it is not finite.  partial (float64, >= grid)
+// receives the per-block sums of squares.  Nothing is launched unless every check passes.
+void privacy_norm(const at::Tensor& w, const at::Tensor& anchor, const at::Tensor& partial, const at::Tensor& stats,
+                  double clip) {
+  need(w, at::kFloat, "w");
+  need(anchor, at::kFloat, "anchor");
+  need(partial, at::kDouble, "partial");
+  need(stats, at::kFloat, "stats");
+  const int64_t n = w.numel();
+  TORCH_CHECK(n > 0 && n % 4 == 0, "privacy_norm: numel % 4");
+  TORCH_CHECK(anchor.numel() == n, "privacy_norm: anchor has ", anchor.numel(), " elements, w ", n);
+  const auto dev = w.device();
+  TORCH_CHECK(anchor.device() == dev && partial.device() == dev && stats.device() == dev,
+              "privacy_norm: tensors on one device");
+  TORCH_CHECK(partial.numel() >= (int64_t)fd_privacy_grid(n), "privacy_norm: partial size");
+  TORCH_CHECK(stats.numel() == 4, "privacy_norm: stats holds 4 floats");
+  TORCH_CHECK(!privacy_overlap(w, anchor), "privacy_norm: anchor overlaps w");
+  TORCH_CHECK(std::isfinite(clip) && clip <= (double)std::numeric_limits<float>::max() && (float)clip > 0.f,
+              "privacy_norm: clip must be finite and > 0");
+  check_rc(fd_privacy_norm(w.data_ptr<float>(), anchor.data_ptr<float>(), partial.data_ptr<double>(),
+                           stats.data_ptr<float>(), (float)clip, n, stream()),
+           "privacy_norm");
+}
+
+// In place: w = clip(w; anchor, stats) + sigma * g, shadow (optional) = bf16(w); stats is read on the
+// device (privacy_norm's output).  Element i of w has the global index 4 * first4 + i of the stream.
+void privacy_apply(const at::Tensor& w, const at::Tensor& anchor, const c10::optional<at::Tensor>& shadow,
+                   const at::Tensor& stats, double sigma, int64_t seed_lo, int64_t seed_hi, int64_t round,
+                   int64_t client, int64_t first4) {
+  need(w, at::kFloat, "w");
+  need(anchor, at::kFloat, "anchor");
+  need_opt(shadow, at::kBFloat16, "shadow");
+  need(stats, at::kFloat, "stats");
+  const bool has_shadow = shadow.has_value() && shadow->defined();
+  const int64_t n = w.numel();
+  TORCH_CHECK(n > 0 && n % 4 == 0, "privacy_apply: numel % 4");
+  TORCH_CHECK(anchor.numel() == n, "privacy_apply: anchor has ", anchor.numel(), " elements, w ", n);
+  if (has_shadow) TORCH_CHECK(shadow->numel() == n, "privacy_apply: shadow size");
+  const auto dev = w.device();
+  TORCH_CHECK(anchor.device() == dev && stats.device() == dev && (!has_shadow || shadow->device() == dev),
+              "privacy_apply: tensors on one device");
+  TORCH_CHECK(stats.numel() == 4, "privacy_apply: stats holds 4 floats");
+  TORCH_CHECK(!privacy_overlap(w, anchor), "privacy_apply: anchor overlaps w");
+  if (has_shadow)
+    TORCH_CHECK(!privacy_overlap(*shadow, w) && !privacy_overlap(*shadow, anchor),
+                "privacy_apply: shadow overlaps w or anchor");
+  TORCH_CHECK(!privacy_overlap(stats, w) && (!has_shadow || !privacy_overlap(stats, *shadow)),
+              "privacy_apply: stats overlaps an output");
+  TORCH_CHECK(std::isfinite(sigma) && sigma >= 0.0 && sigma <= (double)std::numeric_limits<float>::max(),
+              "privacy_apply: sigma must be finite and >= 0");
+  privacy_stream_check(seed_lo, seed_hi, round, client, first4, n, "privacy_apply");
+  check_rc(fd_privacy_apply(w.data_ptr<float>(), anchor.data_ptr<float>(), ptr<void>(shadow), stats.data_ptr<float>(),
+                            (float)sigma, (uint32_t)seed_lo, (uint32_t)seed_hi, round, client, first4, n, stream()),
+           "privacy_apply");
+}
+
+// out[i] = g(4 * first4 + i): the generator privacy_apply adds, alone.
+void privacy_gauss(const at::Tensor& out, int64_t seed_lo, int64_t seed_hi, int64_t round, int64_t client,
+                   int64_t first4) {
+  need(out, at::kFloat, "out");
+  const int64_t n = out.numel();
+  TORCH_CHECK(n > 0 && n % 4 == 0, "privacy_gauss: numel % 4");
+  privacy_stream_check(seed_lo, seed_hi, round, client, first4, n, "privacy_gauss");
+  check_rc(fd_privacy_gauss(out.data_ptr<float>(), (uint32_t)seed_lo, (uint32_t)seed_hi, round, client, first4, n,
+                            stream()),
+           "privacy_gauss");
+}
+
 }  // namespace
 
 #ifndef FD_HOST_VALIDATION
@@ -1994,5 +2093,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("robust_agg", &robust_agg, py::arg("srcs"), py::arg("k"), py::arg("out"), py::arg("shadow") = py::none(),
         py::arg("counts") = py::none());
   m.def("robust_agg_grid", &robust_agg_grid);
+  m.def("privacy_grid", &privacy_grid);
+  m.def("privacy_norm", &privacy_norm, py::arg("w"), py::arg("anchor"), py::arg("partial"), py::arg("stats"),
+        py::arg("clip"));
+  m.def("privacy_apply", &privacy_apply, py::arg("w"), py::arg("anchor"), py::arg("shadow"), py::arg("stats"),
+        py::arg("sigma"), py::arg("seed_lo"), py::arg("seed_hi"), py::arg("round"), py::arg("client"),
+        py::arg("first4") = 0);
+  m.def("privacy_gauss", &privacy_gauss, py::arg("out"), py::arg("seed_lo"), py::arg("seed_hi"), py::arg("round"),
+        py::arg("client"), py::arg("first4") = 0);
 }
 #endif  // FD_HOST_VALIDATION

@@ -709,6 +709,57 @@ int fd_robust_agg(const float* const* src, int M, int k, float* out, void* shado
   }
   return 0;
 }
+// (the grid of fd_server_opt -- csrc/kernels/privacy.hip pv_grid_for)
+int fd_privacy_grid(long long n) { return fd_server_opt_grid(n); }
+namespace {
+bool hc_overlaps(const void* a, long long ab, const void* b, long long bb) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + (uintptr_t)bb && b0 < a0 + (uintptr_t)ab;
+}
+void hc_privacy_stream(long long round, long long client, long long first4, const char* what) {
+  if (round < 0 || round > 0xffffffffll || client < 0 || client > 0xffffffffll || first4 < 0)
+    hc::violations.push_back(std::string(what) + ": round / client / first4");
+}
+}  // namespace
+int fd_privacy_norm(const float* w, const float* anchor, double* partial, float* stats, float clip, long long n,
+                    hipStream_t) {
+  ++hc::calls;
+  // the kernels read n / 4 float4 of w and anchor, write one double per block of partial, and the
+  // finalize reads those and writes the four floats of stats
+  if (n <= 0 || n % 4 != 0) hc::violations.push_back("privacy_norm: n % 4");
+  hc::span(w, n * 4, "privacy_norm w");
+  hc::span(anchor, n * 4, "privacy_norm anchor");
+  hc::span(partial, 8LL * fd_privacy_grid(n), "privacy_norm partial");
+  hc::span(stats, 16, "privacy_norm stats");
+  if (w && anchor && hc_overlaps(w, n * 4, anchor, n * 4)) hc::violations.push_back("privacy_norm: anchor overlaps w");
+  if (!std::isfinite(clip) || !(clip > 0.f)) hc::violations.push_back("privacy_norm: clip");
+  return 0;
+}
+int fd_privacy_apply(float* w, const float* anchor, void* shadow, const float* stats, float sigma, uint32_t, uint32_t,
+                     long long round, long long client, long long first4, long long n, hipStream_t) {
+  ++hc::calls;
+  // the kernel reads stats[1..2], n / 4 float4 of w (and of anchor), writes as many to w and uint2 to
+  // the shadow
+  if (n <= 0 || n % 4 != 0) hc::violations.push_back("privacy_apply: n % 4");
+  hc::span(w, n * 4, "privacy_apply w");
+  hc::span(anchor, n * 4, "privacy_apply anchor");
+  hc::opt_span(shadow, n * 2, "privacy_apply shadow");
+  hc::span(stats, 16, "privacy_apply stats");
+  if (w && anchor && hc_overlaps(w, n * 4, anchor, n * 4)) hc::violations.push_back("privacy_apply: anchor overlaps w");
+  if (shadow && ((w && hc_overlaps(shadow, n * 2, w, n * 4)) || (anchor && hc_overlaps(shadow, n * 2, anchor, n * 4))))
+    hc::violations.push_back("privacy_apply: shadow overlaps w or anchor");
+  if (!std::isfinite(sigma) || !(sigma >= 0.f)) hc::violations.push_back("privacy_apply: sigma");
+  hc_privacy_stream(round, client, first4, "privacy_apply");
+  return 0;
+}
+int fd_privacy_gauss(float* out, uint32_t, uint32_t, long long round, long long client, long long first4, long long n,
+                     hipStream_t) {
+  ++hc::calls;
+  if (n <= 0 || n % 4 != 0) hc::violations.push_back("privacy_gauss: n % 4");
+  hc::span(out, n * 4, "privacy_gauss out");
+  hc_privacy_stream(round, client, first4, "privacy_gauss");
+  return 0;
+}
 }  // extern "C"
 
 // ------------------------------------------------------------------ driver
@@ -1345,6 +1396,77 @@ int main() {
     expect_ok("robust_agg out beside a source", [&] { robust_agg({s3[0], lo, s3[2]}, 1, hi, sh, ct); });
     auto shv = big.narrow(0, n / 2, n / 2).view(bf);
     expect_reject("robust_agg shadow overlaps a source", [&] { robust_agg({s3[0], lo, s3[2]}, 1, out, shv, ct); });
+  }
+  // ---- client-level privacy: w / anchor fp32, the bf16 shadow, one double per block, 4 stats floats
+  {
+    const auto f64 = at::kDouble;
+    const int64_t n = 4096 * 1024 + 4 * 257;  // the grid-stride loop wraps, ragged last block
+    const int64_t grid = fd_privacy_grid(n);
+    auto w = T_({n}, f32), a = T_({n}, f32), sh = T_({n}, bf), part = T_({grid}, f64), st = T_({4}, f32);
+    const int64_t top = (int64_t(1) << 32) - 1;
+    expect_ok("privacy_norm", [&] { privacy_norm(w, a, part, st, 0.5); });
+    expect_ok("privacy_apply", [&] { privacy_apply(w, a, sh, st, 0.01, 1, 2, 3, 4, 0); });
+    expect_ok("privacy_apply no shadow, sigma 0", [&] { privacy_apply(w, a, none, st, 0.0, 0, 0, 0, 0, 0); });
+    expect_ok("privacy_apply top words, first4 past 2^32", [&] {
+      privacy_apply(w, a, sh, st, 0.01, top, top, top, top, (int64_t(1) << 32) - 8);
+    });
+    expect_ok("privacy_gauss", [&] { privacy_gauss(w, 1, 2, 3, 4, 0); });
+    auto w8 = T_({2048}, f32), a8 = T_({2048}, f32), p8 = T_({2}, f64);
+    expect_ok("privacy_norm small", [&] { privacy_norm(w8, a8, p8, st, 1.0); });
+    expect_ok("privacy_apply small", [&] { privacy_apply(w8, a8, none, st, 0.5, 0, 0, 0, 1, 7); });
+    auto srt = T_({n - 4}, f32), shs = T_({n - 4}, bf), part_short = T_({grid - 1}, f64), st3 = T_({3}, f32),
+         st8 = T_({8}, f32);
+    expect_reject("privacy_norm short anchor", [&] { privacy_norm(w, srt, part, st, 0.5); });
+    expect_reject("privacy_norm short partial", [&] { privacy_norm(w, a, part_short, st, 0.5); });
+    expect_reject("privacy_norm short stats", [&] { privacy_norm(w, a, part, st3, 0.5); });
+    expect_reject("privacy_norm long stats", [&] { privacy_norm(w, a, part, st8, 0.5); });
+    expect_reject("privacy_apply short anchor", [&] { privacy_apply(w, srt, sh, st, 0.01, 1, 2, 3, 4, 0); });
+    expect_reject("privacy_apply short shadow", [&] { privacy_apply(w, a, shs, st, 0.01, 1, 2, 3, 4, 0); });
+    expect_reject("privacy_apply short stats", [&] { privacy_apply(w, a, sh, st3, 0.01, 1, 2, 3, 4, 0); });
+    auto wb = T_({n}, bf), shf = T_({n}, f32), partf = T_({grid}, f32), std_ = T_({4}, f64);
+    expect_reject("privacy_norm w dtype", [&] { privacy_norm(wb, a, part, st, 0.5); });
+    expect_reject("privacy_norm anchor dtype", [&] { privacy_norm(w, wb, part, st, 0.5); });
+    expect_reject("privacy_norm partial dtype", [&] { privacy_norm(w, a, partf, st, 0.5); });
+    expect_reject("privacy_norm stats dtype", [&] { privacy_norm(w, a, part, std_, 0.5); });
+    expect_reject("privacy_apply shadow dtype", [&] { privacy_apply(w, a, shf, st, 0.01, 1, 2, 3, 4, 0); });
+    expect_reject("privacy_apply stats dtype", [&] { privacy_apply(w, a, sh, std_, 0.01, 1, 2, 3, 4, 0); });
+    expect_reject("privacy_gauss dtype", [&] { privacy_gauss(wb, 1, 2, 3, 4, 0); });
+    auto xt = T_({2, n / 2}, f32).t();
+    expect_reject("privacy_norm non-contiguous", [&] { privacy_norm(xt, a, part, st, 0.5); });
+    expect_reject("privacy_apply non-contiguous anchor", [&] { privacy_apply(w, xt, sh, st, 0.01, 1, 2, 3, 4, 0); });
+    auto w6 = T_({2046}, f32), a6 = T_({2046}, f32), w0 = T_({0}, f32);
+    expect_reject("privacy_norm numel % 4", [&] { privacy_norm(w6, a6, p8, st, 1.0); });
+    expect_reject("privacy_apply numel % 4", [&] { privacy_apply(w6, a6, none, st, 0.0, 0, 0, 0, 0, 0); });
+    expect_reject("privacy_gauss numel % 4", [&] { privacy_gauss(w6, 0, 0, 0, 0, 0); });
+    expect_reject("privacy_gauss empty", [&] { privacy_gauss(w0, 0, 0, 0, 0, 0); });
+    const double inf = HUGE_VAL;
+    expect_reject("privacy_norm clip 0", [&] { privacy_norm(w, a, part, st, 0.0); });
+    expect_reject("privacy_norm clip < 0", [&] { privacy_norm(w, a, part, st, -1.0); });
+    expect_reject("privacy_norm clip inf", [&] { privacy_norm(w, a, part, st, inf); });
+    expect_reject("privacy_norm clip NaN", [&] { privacy_norm(w, a, part, st, std::nan("")); });
+    expect_reject("privacy_norm clip beyond fp32", [&] { privacy_norm(w, a, part, st, 1e300); });
+    expect_reject("privacy_norm clip below fp32", [&] { privacy_norm(w, a, part, st, 1e-300); });
+    expect_reject("privacy_apply sigma < 0", [&] { privacy_apply(w, a, sh, st, -0.01, 1, 2, 3, 4, 0); });
+    expect_reject("privacy_apply sigma inf", [&] { privacy_apply(w, a, sh, st, inf, 1, 2, 3, 4, 0); });
+    expect_reject("privacy_apply sigma NaN", [&] { privacy_apply(w, a, sh, st, std::nan(""), 1, 2, 3, 4, 0); });
+    expect_reject("privacy_apply round < 0", [&] { privacy_apply(w, a, sh, st, 0.01, 1, 2, -1, 4, 0); });
+    expect_reject("privacy_apply client < 0", [&] { privacy_apply(w, a, sh, st, 0.01, 1, 2, 3, -1, 0); });
+    expect_reject("privacy_apply first4 < 0", [&] { privacy_apply(w, a, sh, st, 0.01, 1, 2, 3, 4, -1); });
+    expect_reject("privacy_apply round 2^32", [&] { privacy_apply(w, a, sh, st, 0.01, 1, 2, top + 1, 4, 0); });
+    expect_reject("privacy_apply seed word 2^32", [&] { privacy_apply(w, a, sh, st, 0.01, top + 1, 2, 3, 4, 0); });
+    expect_reject("privacy_gauss client < 0", [&] { privacy_gauss(w, 1, 2, 3, -4, 0); });
+    expect_reject("privacy_gauss first4 < 0", [&] { privacy_gauss(w, 1, 2, 3, 4, -8); });
+    // anchor / shadow as a window of w's allocation
+    auto big = T_({2 * n}, f32);
+    auto lo = big.narrow(0, 0, n), mid = big.narrow(0, n / 2, n), hi = big.narrow(0, n, n);
+    expect_reject("privacy_norm anchor is w", [&] { privacy_norm(w, w, part, st, 0.5); });
+    expect_reject("privacy_norm anchor overlaps w", [&] { privacy_norm(lo, mid, part, st, 0.5); });
+    expect_ok("privacy_norm anchor beside w", [&] { privacy_norm(lo, hi, part, st, 0.5); });
+    expect_reject("privacy_apply anchor overlaps w", [&] { privacy_apply(lo, mid, sh, st, 0.01, 1, 2, 3, 4, 0); });
+    expect_ok("privacy_apply anchor beside w", [&] { privacy_apply(lo, hi, sh, st, 0.01, 1, 2, 3, 4, 0); });
+    auto shv = big.narrow(0, n / 2, n / 2).view(bf);
+    expect_reject("privacy_apply shadow overlaps w", [&] { privacy_apply(lo, a, shv, st, 0.01, 1, 2, 3, 4, 0); });
+    expect_reject("privacy_apply shadow overlaps anchor", [&] { privacy_apply(w, lo, shv, st, 0.01, 1, 2, 3, 4, 0); });
   }
   // ---- embedding backward (work = pieces + LayerNorm partials)
   {

@@ -147,10 +147,12 @@ def _virtual(argv):
             "round": r, "fedavg_ms": h["fedavg_ms"], "aggregated_confusion": h["aggregated_confusion"],
             "aggregated_accuracy": 100.0 * (tp + tn) / max(tp + tn + fp + fn, 1),
             **({k: h[k] for k in ("delta_l2", "step_l2") if k in h}),  # (a server optimizer's step)
+            **({k: h[k] for k in ("privacy_epsilon",) if k in h}),  # (--privacy-clip: spent so far, an upper bound)
             "clients": [{"client": c["client"], "local_test": c["local_test"], "aggregated_test": c["aggregated_test"],
                          "epoch_losses": c["train"]["epoch_losses"], "train_steps": c["train"]["steps"],
                          "rel_l2_local_to_aggregate": c["rel_l2_local_to_aggregate"],
                          "l2_local_to_start": c["l2_local_to_start"],
+                         **({k: c[k] for k in ("update_l2", "clipped", "privacy_sigma") if k in c}),
                          **({"teacher_test": c["teacher_test"]} if "teacher_test" in c else {})}
                         for c in h["clients"]]})
     if cfg.save_checkpoints:

@@ -17,7 +17,7 @@ from dataclasses import dataclass, field
 from typing import Optional
 
 
-_OPTIONAL_INTS = ("drop_client", "drop_round", "num_clients", "poison_client", "poison_round")
+_OPTIONAL_INTS = ("drop_client", "drop_round", "num_clients", "poison_client", "poison_round", "privacy_seed")
 
 
 @dataclass
@@ -79,6 +79,13 @@ class FedConfig:
     # "trimmed_mean": k = floor(trim_ratio * M) of the M participating clients; "median": k = (M - 1) // 2
     aggregator: str = "mean"                # "mean" | "trimmed_mean" | "median"
     trim_ratio: float = 0.2                 # trimmed_mean: share trimmed at each end, in [0, 0.5)
+    # Client-level differential privacy (parallel/privacy.py; DP-FedAvg, McMahan et al., ICLR 2018): every
+    # sampled client clips its round update w - w_global to L2 norm privacy_clip and adds
+    # N(0, (privacy_noise * privacy_clip)^2 / M) before the exchange, M the round's sampled clients.  0: off
+    privacy_clip: float = 0.0               # C, the bound on a client's update norm
+    privacy_noise: float = 0.0              # z, the noise multiplier: the sum carries std z * C
+    privacy_delta: float = 1e-5             # the delta of the reported (epsilon, delta)
+    privacy_seed: Optional[int] = None      # None: 64 bits of os.urandom per process; an int: fixed (tests)
     participation: float = 1.0              # fraction of clients aggregated per round
     timeout_s: float = 300.0                # server.py:10 / client1.py:22
     heartbeat_s: float = 1.0                # failure detection (parallel/health.py); 0 disables

@@ -30,6 +30,7 @@ from ..models import DDoSClassifier, DistilBertConfig
 from ..parallel import comm, health
 from ..parallel.dp import DPShardLoader, GradSync, dp_seed_offset, make_topology
 from ..parallel.fedavg import broadcast_model, fedavg_
+from ..parallel.privacy import check_privacy_config, make_privatizer
 from ..parallel.robust import check_robust_config, make_robust, most_trimmed, robust_aggregate_
 from ..parallel.server_opt import check_server_config, make_server_optimizer
 from ..utils import checkpoint as ck
@@ -109,6 +110,7 @@ class FederatedClient:
         cfg, log = self.cfg, self.log
         check_server_config(cfg)  # (an unknown kind, a bad value, or transport=tcp: refused before any work)
         check_robust_config(cfg)  # (likewise: an unknown aggregator, tcp, weighted_fedavg)
+        check_privacy_config(cfg, self.topo.gpus_per_client)  # (a bad clip / noise / delta, weighted_fedavg, replicas)
         log.phase("Starting client")
         with self.timer("preprocess"):
             if self.frame is None:
@@ -184,6 +186,11 @@ class FederatedClient:
         if self.robust is not None:
             log.info(f"robust aggregation: {self.robust.aggregator}"
                      + (f" (trim_ratio {self.robust.trim_ratio:g})" if self.robust.aggregator == "trimmed_mean" else ""))
+        # Client-level differential privacy (parallel/privacy.py; None: privacy_clip == 0, today's path)
+        self.privacy = make_privatizer(cfg, self.topo.gpus_per_client)
+        self._privacy_anchor = None
+        if self.privacy is not None:
+            log.info(_privacy_line(self.privacy, cfg.rounds))
         self.health = None
         if self.di.distributed and cfg.heartbeat_s > 0 and cfg.transport != "tcp":
             self.health = health.start(cfg.heartbeat_s, cfg.heartbeat_stale_s, cfg.timeout_s)
@@ -278,6 +285,12 @@ class FederatedClient:
         log.phase(f"Starting round {r + 1}/{cfg.rounds}")
         opt = make_optimizer(model, cfg, r, cfg.rounds, cfg.epochs * len(self.train_loader))
         opt.reset_state()  # a fresh Adam every round (client1.py:380), "has state" row flags included
+        if self.privacy is not None:
+            # the round's starting weights: what the update is measured (and clipped) against
+            if self._privacy_anchor is None:
+                self._privacy_anchor = torch.empty_like(model.arena.master)
+            with torch.no_grad():
+                self._privacy_anchor.copy_(model.arena.master)
         opt_path = os.path.join(cfg.out_dir, f"client{self.client_id}_optim.pth")
         if cfg.save_optimizer and r == self.start_round:
             ck.load_optimizer(opt, opt_path)
@@ -325,6 +338,26 @@ class FederatedClient:
             except health.PeerFailure as e:
                 log.info(f"[ERROR] {e}; aborting round {r + 1} (restart resumes from the last completed round)")
                 raise
+        priv = None
+        if self.privacy is not None and self.idx in part:
+            # what is sent is the privatized copy (the local metrics and clientN_model.pth above describe
+            # the trained weights); privatize, then poison: a liar lies whatever the protocol
+            A = model.arena
+            priv = self.privacy.privatize_(A.master, self._privacy_anchor, self.idx, r, len(part), shadow=A.shadow,
+                                           arena=A)
+            if A.shadow is not None:
+                model.mark_shadow_synced()
+            else:
+                model.sync_shadow(force=True)
+            priv = _privacy_fields(priv, self.privacy, r + 1)
+            log.info(f"privatized update: |w - w_global| = {priv['update_l2']:.6g} (clipped={priv['clipped']}), "
+                     f"sigma = {priv['privacy_sigma']:.6g}, epsilon <= {priv['privacy_epsilon']:.6g} at delta "
+                     f"{self.privacy.delta:g} after {r + 1} round(s) (an upper bound: no subsampling amplification)")
+        if self.privacy is not None:
+            lost = [c for c in part if faults.dropped(cfg, c, r)]
+            if lost:
+                log.info(f"[WARN] sampled client(s) {[c + 1 for c in lost]} dropped from round {r + 1}: the sum "
+                         f"carries less noise than the accountant assumes")
         if faults.poison_(model.arena.master, cfg, self.idx, r):  # (this client lies: utils/faults.py)
             log.info(f"[FAULT] sending a poisoned update ({cfg.poison_kind})")
         with self.timer("fedavg"):
@@ -380,6 +413,10 @@ class FederatedClient:
             rec.update(delta_l2=norms["delta_l2"], step_l2=norms["step_l2"])
         if trim is not None:
             rec.update(trimmed_share=trim["trimmed_share"], k=trim["k"])
+        if priv is not None:
+            rec.update(priv)
+        elif self.privacy is not None:  # (not sampled this round: nothing of this client was released)
+            rec.update(privacy_epsilon=self.privacy.epsilon(r + 1))
         self.history.append(rec)
         if self.writer:
             ck.save_fed_state(cfg.out_dir, self.client_id, {"completed_rounds": r + 1, "history": self.history})
@@ -441,12 +478,30 @@ class FederatedClient:
                             "fedavg_ms": v[7]} for i, v in enumerate(allv)],
                "rounds": self.cfg.rounds, "world_size": self.di.world_size,
                "gpus_per_client": self.topo.gpus_per_client, "phases_s": self.timer.summary()}
+        if getattr(self, "privacy", None) is not None:
+            # spent over the whole run, without subsampling amplification: an upper bound
+            rep.update(privacy_epsilon=self.privacy.epsilon(self.cfg.rounds), privacy_delta=self.privacy.delta,
+                       privacy_clip=self.privacy.clip, privacy_noise=self.privacy.noise_multiplier)
         if self.di.is_main:
             path = os.path.join(self.cfg.out_dir, "federated_report.json")
             with open(path, "w") as f:
                 json.dump(rep, f, indent=1)
             self.log.info(f"federated report written to {path}")
         return rep
+
+
+def _privacy_line(privacy, rounds: int) -> str:
+    """One log line for a private run: the mechanism and what ``rounds`` rounds of it spend."""
+    return (f"client-level privacy: clip C = {privacy.clip:g}, noise multiplier z = {privacy.noise_multiplier:g} "
+            f"(each of a round's M sampled clients adds N(0, (z C)^2 / M)); {rounds} round(s) spend epsilon <= "
+            f"{privacy.epsilon(rounds):.6g} at delta {privacy.delta:g} (an upper bound: no subsampling "
+            f"amplification is credited)")
+
+
+def _privacy_fields(rep: Dict, privacy, rounds_done: int) -> Dict:
+    """A record's privacy keys from ``Privatizer.privatize_``'s report."""
+    return {"update_l2": rep["update_l2"], "clipped": rep["clipped"], "privacy_sigma": rep["sigma"],
+            "privacy_epsilon": privacy.epsilon(rounds_done)}
 
 
 def _trim_line(trim: Dict) -> str:
@@ -543,6 +598,12 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
     3-rank gloo run bit for bit).  A poisoned client (``cfg.poison_client``, utils/faults.py) sends a
     changed copy of its weights; its local metrics are those of the weights it trained.
 
+    With client-level privacy (``cfg.privacy_clip``, parallel/privacy.py) every client's copy is clipped
+    and noised against the round's start before it is aggregated (and before a poisoner changes it) --
+    the call ``run_round`` makes on its master -- and each client record carries ``update_l2`` /
+    ``clipped`` / ``privacy_sigma`` / ``privacy_epsilon``, the round record ``privacy_epsilon``
+    (tests/test_privacy_cpu.py: equal to the 2-rank gloo run bit for bit under a fixed seed).
+
     Returns ``rounds`` (one record per round: per-client local / aggregated metrics, the pooled
     aggregated confusion, the FedAvg time) plus the LAST round's ``clients`` /
     ``aggregated_confusion`` / ``fedavg_ms`` at the top level (the 1-round API of earlier rounds).
@@ -567,6 +628,8 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
         client.log.info("[WARN] the model changed since the server optimizer was built: server state reset")
         server.reset(model)
     robust = make_robust(cfg)  # (None: the plain mean -- _average_masters, untouched)
+    # the job's Privatizer (None: privacy_clip == 0) -- one object, so one seed, for every virtual client
+    privacy = getattr(client, "privacy", None)
     t_init = teacher.arena.master.detach().clone() if teacher is not None else None
     say = progress or (lambda msg: None)
     # per-client state that survives the rounds (a real client's process keeps it)
@@ -620,6 +683,9 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
             c["torch_counter"] = model.torch_counter
             local = _metrics_record(evaluate_model(model, test, name=f"Client {v + 1} local test"))
             locals_.append(A.master.detach().clone())
+            if privacy is not None:  # (clip + noise against the round's start; then a liar may still lie)
+                rec.update(_privacy_fields(privacy.privatize_(locals_[-1], glob, v, r, n_clients, arena=A), privacy,
+                                           r + 1))
             faults.poison_(locals_[-1], cfg, v, r)  # (a lying client: what it sends, not what it evaluated)
             rec.update({"train": tr, "train_wall_s": time.perf_counter() - t0, "local_test": local})
             # client drift: how far the local epochs moved this client from the round's start
@@ -656,6 +722,11 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
             hist[-1].update(trimmed_share=trim["trimmed_share"], k=trim["k"])
             client.log.info(_trim_line(trim))
             say(f"round {r + 1}/{rounds} " + _trim_line(trim))
+        if privacy is not None:
+            hist[-1].update(privacy_epsilon=privacy.epsilon(r + 1))
+            say(f"round {r + 1}/{rounds} privacy: epsilon <= {hist[-1]['privacy_epsilon']:.6g} at delta "
+                f"{privacy.delta:g} (an upper bound: no subsampling amplification), clipped "
+                f"{[c['clipped'] for c in recs]}")
         (tn, fp), (fn, tp) = pooled
         say(f"round {r + 1}/{rounds} aggregate: pooled acc {100.0 * (tp + tn) / max(tp + tn + fp + fn, 1):.3f} %")
     last = hist[-1]

@@ -1167,3 +1167,41 @@ def robust_agg(srcs, k, out, shadow=None, counts=None):
     block how often each slot's value was trimmed (columns >= M: 0) and, in column 16, the non-finite
     outputs; every entry is written on every launch."""
     ext().robust_agg(list(srcs), int(k), out, shadow, counts)
+
+
+def _seed_words(seed):
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"privacy seed must lie in [0, 2^64), got {seed}")
+    return seed & 0xFFFFFFFF, seed >> 32
+
+
+def privacy_grid(n):
+    """Blocks of a ``privacy_norm`` / ``privacy_apply`` / ``privacy_gauss`` launch over ``n`` floats
+    (``partial`` holds one double per block)."""
+    return int(ext().privacy_grid(int(n)))
+
+
+def privacy_norm(w, anchor, partial, stats, clip):
+    """``stats`` (fp32, 4) = [|w - anchor|_2, scale, flag, 0] in two stream-ordered launches
+    (privacy.hip): per-block sums of squares into ``partial`` (float64, >= ``privacy_grid(n)``, every
+    entry written), then a one-block finalize.  flag 0 / scale 1: the norm is <= ``clip``; flag 1 /
+    scale ``clip / norm``: above it; flag 2 / scale 0: the norm is not finite."""
+    ext().privacy_norm(w, anchor, partial, stats, float(clip))
+
+
+def privacy_apply(w, anchor, shadow, stats, sigma, seed, round, client, first4=0):
+    """In place on ``w``, ``stats`` (``privacy_norm``'s) read on the device: the clipped update
+    (``parallel.privacy.torch_privatize_`` is the specification) plus ``sigma * g`` when ``sigma != 0``;
+    ``shadow`` (optional) = bf16(w).  Element i draws the Gaussian of global index ``4 * first4 + i``
+    of the stream (seed, round, client)."""
+    lo, hi = _seed_words(seed)
+    ext().privacy_apply(w, anchor, shadow, stats, float(sigma), lo, hi, int(round), int(client), int(first4))
+
+
+def privacy_gauss(out, seed, round, client, first4=0):
+    """``out[i]`` = the standard Gaussian of global index ``4 * first4 + i`` of the stream (seed, round,
+    client): Philox4x32-10 + Box-Muller, the device function ``privacy_apply`` adds
+    (``parallel.privacy.torch_gauss`` is its fp64 host mirror)."""
+    lo, hi = _seed_words(seed)
+    ext().privacy_gauss(out, lo, hi, int(round), int(client), int(first4))
