@@ -161,6 +161,13 @@ int fd_privacy_apply(float* w, const float* anchor, void* shadow, const float* s
                      hipStream_t st);
 int fd_privacy_gauss(float* out, uint32_t seed_lo, uint32_t seed_hi, long long round, long long client,
                      long long first4, long long n, hipStream_t st);
+int fd_quant_grid(long long n);
+long long fd_quant_words(long long n, int bits);
+int fd_quant_encode(const float* w, const float* anchor, float* residual, int32_t* payload, double* partial,
+                    double* stats, int bits, int stochastic, uint32_t seed_lo, uint32_t seed_hi, long long round,
+                    long long client, long long first, long long n, hipStream_t st);
+int fd_quant_decode_mean(const int32_t* const* src, int M, const float* anchor, float* out, void* shadow, int bits,
+                         long long n, hipStream_t st);
 }
 
 namespace {
@@ -1971,6 +1978,97 @@ void privacy_gauss(const at::Tensor& out, int64_t seed_lo, int64_t seed_hi, int6
            "privacy_gauss");
 }
 
+// Quantized update exchange (compress.hip).  A payload of n floats at `bits` (8 or 4) is one int32
+// tensor: n * bits / 32 words of codes, then n / 64 words of fp32 scale bit patterns.
+int64_t quant_grid(int64_t n) { return (int64_t)fd_quant_grid(n); }
+
+int64_t quant_words(int64_t n, int64_t bits) {
+  TORCH_CHECK(bits == 8 || bits == 4, "quant_words: bits must be 8 or 4, got ", bits);
+  TORCH_CHECK(n > 0 && n % 64 == 0 && n <= (std::numeric_limits<int64_t>::max() >> 1) / 8,
+              "quant_words: numel % 64, got ", n);
+  return (int64_t)fd_quant_words(n, (int)bits);
+}
+
+// payload = the int8 / int4 codes and per-64 scales of v = (w - anchor) + residual; residual
+// (optional) = the quantization error, in place; stats (float64, 4) = {|v|, |e'|, bad groups, 0};
+// partial (float64, >= 3 * grid) receives the per-block sums.  Element i draws the stochastic word
+// of global index 64 * first + i of the stream (seed, round, client).  Nothing is launched unless
+// every check passes; no two of w, anchor, residual, payload, partial, stats overlap.
+void quant_encode(const at::Tensor& w, const at::Tensor& anchor, const c10::optional<at::Tensor>& residual,
+                  const at::Tensor& payload, const at::Tensor& partial, const at::Tensor& stats, int64_t bits,
+                  bool stochastic, int64_t seed_lo, int64_t seed_hi, int64_t round, int64_t client, int64_t first) {
+  need(w, at::kFloat, "w");
+  need(anchor, at::kFloat, "anchor");
+  need_opt(residual, at::kFloat, "residual");
+  need(payload, at::kInt, "payload");
+  need(partial, at::kDouble, "partial");
+  need(stats, at::kDouble, "stats");
+  const bool has_res = residual.has_value() && residual->defined();
+  const int64_t n = w.numel();
+  const int64_t words = quant_words(n, bits);
+  TORCH_CHECK(anchor.numel() == n, "quant_encode: anchor has ", anchor.numel(), " elements, w ", n);
+  if (has_res) TORCH_CHECK(residual->numel() == n, "quant_encode: residual has ", residual->numel(), " elements, w ", n);
+  TORCH_CHECK(payload.numel() == words, "quant_encode: payload has ", payload.numel(), " words, expected ", words);
+  const auto dev = w.device();
+  TORCH_CHECK(anchor.device() == dev && payload.device() == dev && partial.device() == dev && stats.device() == dev &&
+                  (!has_res || residual->device() == dev),
+              "quant_encode: tensors on one device");
+  TORCH_CHECK(partial.numel() >= 3 * (int64_t)fd_quant_grid(n), "quant_encode: partial size");
+  TORCH_CHECK(stats.numel() == 4, "quant_encode: stats holds 4 doubles");
+  std::vector<const at::Tensor*> bufs = {&w, &anchor, &payload, &partial, &stats};
+  if (has_res) bufs.push_back(&*residual);
+  for (size_t i = 0; i < bufs.size(); ++i)
+    for (size_t j = i + 1; j < bufs.size(); ++j)
+      TORCH_CHECK(!privacy_overlap(*bufs[i], *bufs[j]), "quant_encode: buffers ", i, " and ", j, " overlap");
+  const int64_t w32 = int64_t(1) << 32;
+  TORCH_CHECK(seed_lo >= 0 && seed_lo < w32 && seed_hi >= 0 && seed_hi < w32, "quant_encode: seed words in [0, 2^32)");
+  TORCH_CHECK(round >= 0 && round < w32, "quant_encode: round in [0, 2^32), got ", round);
+  TORCH_CHECK(client >= 0 && client < w32, "quant_encode: client in [0, 2^32), got ", client);
+  TORCH_CHECK(first >= 0 && first <= (std::numeric_limits<int64_t>::max() - n / 4) / 16,
+              "quant_encode: first >= 0, got ", first);
+  check_rc(fd_quant_encode(w.data_ptr<float>(), anchor.data_ptr<float>(), ptr<float>(residual),
+                           payload.data_ptr<int32_t>(), partial.data_ptr<double>(), stats.data_ptr<double>(),
+                           (int)bits, stochastic ? 1 : 0, (uint32_t)seed_lo, (uint32_t)seed_hi, round, client, first, n,
+                           stream()),
+           "quant_encode");
+}
+
+// out = anchor + the mean of the M decoded payloads (1 <= M <= 16, in the given order), shadow
+// (optional) = bf16(out).  out and shadow overlap no input.
+void quant_decode_mean(const std::vector<at::Tensor>& payloads, const at::Tensor& anchor, const at::Tensor& out,
+                       const c10::optional<at::Tensor>& shadow, int64_t bits) {
+  const int64_t M = (int64_t)payloads.size();
+  TORCH_CHECK(M >= 1 && M <= 16, "quant_decode_mean: 1 <= M <= 16 payloads, got ", M);
+  need(anchor, at::kFloat, "anchor");
+  need(out, at::kFloat, "out");
+  need_opt(shadow, at::kBFloat16, "shadow");
+  const bool has_shadow = shadow.has_value() && shadow->defined();
+  const int64_t n = out.numel();
+  const int64_t words = quant_words(n, bits);
+  TORCH_CHECK(anchor.numel() == n, "quant_decode_mean: anchor has ", anchor.numel(), " elements, out ", n);
+  if (has_shadow) TORCH_CHECK(shadow->numel() == n, "quant_decode_mean: shadow size");
+  const auto dev = out.device();
+  TORCH_CHECK(anchor.device() == dev && (!has_shadow || shadow->device() == dev),
+              "quant_decode_mean: tensors on one device");
+  TORCH_CHECK(!privacy_overlap(out, anchor), "quant_decode_mean: out overlaps anchor");
+  if (has_shadow)
+    TORCH_CHECK(!privacy_overlap(*shadow, out) && !privacy_overlap(*shadow, anchor),
+                "quant_decode_mean: shadow overlaps out or anchor");
+  const int32_t* ptrs[16];
+  for (int64_t s = 0; s < M; ++s) {
+    need(payloads[s], at::kInt, "payload");
+    TORCH_CHECK(payloads[s].device() == dev, "quant_decode_mean: tensors on one device");
+    TORCH_CHECK(payloads[s].numel() == words, "quant_decode_mean: payload ", s, " has ", payloads[s].numel(),
+                " words, expected ", words);
+    TORCH_CHECK(!privacy_overlap(payloads[s], out) && (!has_shadow || !privacy_overlap(payloads[s], *shadow)),
+                "quant_decode_mean: an output overlaps payload ", s);
+    ptrs[s] = payloads[s].data_ptr<int32_t>();
+  }
+  check_rc(fd_quant_decode_mean(ptrs, (int)M, anchor.data_ptr<float>(), out.data_ptr<float>(), ptr<void>(shadow),
+                                (int)bits, n, stream()),
+           "quant_decode_mean");
+}
+
 }  // namespace
 
 #ifndef FD_HOST_VALIDATION
@@ -2101,5 +2199,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("first4") = 0);
   m.def("privacy_gauss", &privacy_gauss, py::arg("out"), py::arg("seed_lo"), py::arg("seed_hi"), py::arg("round"),
         py::arg("client"), py::arg("first4") = 0);
+  m.def("quant_grid", &quant_grid);
+  m.def("quant_words", &quant_words);
+  m.def("quant_encode", &quant_encode, py::arg("w"), py::arg("anchor"), py::arg("residual"), py::arg("payload"),
+        py::arg("partial"), py::arg("stats"), py::arg("bits"), py::arg("stochastic"), py::arg("seed_lo"),
+        py::arg("seed_hi"), py::arg("round"), py::arg("client"), py::arg("first") = 0);
+  m.def("quant_decode_mean", &quant_decode_mean, py::arg("payloads"), py::arg("anchor"), py::arg("out"),
+        py::arg("shadow") = py::none(), py::arg("bits") = 8);
 }
 #endif  // FD_HOST_VALIDATION

@@ -760,6 +760,70 @@ int fd_privacy_gauss(float* out, uint32_t, uint32_t, long long round, long long 
   hc_privacy_stream(round, client, first4, "privacy_gauss");
   return 0;
 }
+// (the grid of fd_server_opt -- csrc/kernels/compress.hip qz_grid_for)
+int fd_quant_grid(long long n) { return fd_server_opt_grid(n); }
+long long fd_quant_words(long long n, int bits) {
+  if (n <= 0 || n % 64 != 0 || (bits != 8 && bits != 4) || n > 0x3fffffffffffffffll / 8) return 0;
+  return n * bits / 32 + n / 64;
+}
+int fd_quant_encode(const float* w, const float* anchor, float* residual, int32_t* payload, double* partial,
+                    double* stats, int bits, int, uint32_t, uint32_t, long long round, long long client,
+                    long long first, long long n, hipStream_t) {
+  ++hc::calls;
+  // the kernel reads n / 4 float4 of w, anchor (and residual, which it also writes), writes
+  // fd_quant_words int32 of payload and three doubles per block of partial; the finalize reads those
+  // and writes the four doubles of stats
+  if (n <= 0 || n % 64 != 0) hc::violations.push_back("quant_encode: n % 64");
+  if (bits != 8 && bits != 4) {
+    hc::violations.push_back("quant_encode: bits");
+    return 0;
+  }
+  const long long words = fd_quant_words(n, bits);
+  hc::span(w, n * 4, "quant_encode w");
+  hc::span(anchor, n * 4, "quant_encode anchor");
+  hc::opt_span(residual, n * 4, "quant_encode residual");
+  hc::span(payload, words * 4, "quant_encode payload");
+  hc::span(partial, 3 * 8LL * fd_quant_grid(n), "quant_encode partial");
+  hc::span(stats, 32, "quant_encode stats");
+  const void* bufs[6] = {w, anchor, residual, payload, partial, stats};
+  const long long bytes[6] = {n * 4, n * 4, n * 4, words * 4, 3 * 8LL * fd_quant_grid(n), 32};
+  for (int i = 0; i < 6; ++i)
+    for (int j = i + 1; j < 6; ++j)
+      if (bufs[i] && bufs[j] && hc_overlaps(bufs[i], bytes[i], bufs[j], bytes[j]))
+        hc::violations.push_back("quant_encode: buffers overlap");
+  if (round < 0 || round > 0xffffffffll || client < 0 || client > 0xffffffffll || first < 0 ||
+      first > (0x7fffffffffffffffll - n / 4) / 16)
+    hc::violations.push_back("quant_encode: round / client / first");
+  return 0;
+}
+int fd_quant_decode_mean(const int32_t* const* src, int M, const float* anchor, float* out, void* shadow, int bits,
+                         long long n, hipStream_t) {
+  ++hc::calls;
+  // the kernel reads fd_quant_words int32 of each of the M payloads and n / 4 float4 of anchor, writes
+  // as many float4 to out (and uint2 to the shadow)
+  if (n <= 0 || n % 64 != 0) hc::violations.push_back("quant_decode_mean: n % 64");
+  if (M < 1 || M > 16 || (bits != 8 && bits != 4)) {
+    hc::violations.push_back("quant_decode_mean: M / bits");
+    return 0;
+  }
+  const long long words = fd_quant_words(n, bits);
+  hc::span(anchor, n * 4, "quant_decode_mean anchor");
+  hc::span(out, n * 4, "quant_decode_mean out");
+  hc::opt_span(shadow, n * 2, "quant_decode_mean shadow");
+  if (anchor && out && hc_overlaps(anchor, n * 4, out, n * 4)) hc::violations.push_back("quant_decode_mean: out overlaps anchor");
+  if (shadow && ((out && hc_overlaps(shadow, n * 2, out, n * 4)) || (anchor && hc_overlaps(shadow, n * 2, anchor, n * 4))))
+    hc::violations.push_back("quant_decode_mean: shadow overlaps out or anchor");
+  if (!src) {
+    hc::violations.push_back("quant_decode_mean: no payloads");
+    return 0;
+  }
+  for (int s = 0; s < M; ++s) {
+    hc::span(src[s], words * 4, "quant_decode_mean payload");
+    if (src[s] && ((out && hc_overlaps(src[s], words * 4, out, n * 4)) || (shadow && hc_overlaps(src[s], words * 4, shadow, n * 2))))
+      hc::violations.push_back("quant_decode_mean: an output overlaps a payload");
+  }
+  return 0;
+}
 }  // extern "C"
 
 // ------------------------------------------------------------------ driver
@@ -1467,6 +1531,104 @@ int main() {
     auto shv = big.narrow(0, n / 2, n / 2).view(bf);
     expect_reject("privacy_apply shadow overlaps w", [&] { privacy_apply(lo, a, shv, st, 0.01, 1, 2, 3, 4, 0); });
     expect_reject("privacy_apply shadow overlaps anchor", [&] { privacy_apply(w, lo, shv, st, 0.01, 1, 2, 3, 4, 0); });
+  }
+  // ---- quantized exchange: w / anchor / residual fp32, the int32 payload, three doubles per block
+  {
+    const auto f64 = at::kDouble;
+    const int64_t n = 4096 * 1024 + 64 * 5;  // the grid-stride loop wraps, ragged last sweep
+    const int64_t grid = fd_quant_grid(n), w8 = fd_quant_words(n, 8), w4 = fd_quant_words(n, 4);
+    auto w = T_({n}, f32), a = T_({n}, f32), e = T_({n}, f32), sh = T_({n}, bf), out = T_({n}, f32);
+    auto p8 = T_({w8}, i32), p4 = T_({w4}, i32), part = T_({3 * grid}, f64), st = T_({4}, f64);
+    const int64_t top = (int64_t(1) << 32) - 1;
+    if (quant_words(n, 8) != n / 4 + n / 64 || quant_words(n, 4) != n / 8 + n / 64) {
+      std::printf("FAIL quant_words: %lld / %lld words\n", (long long)quant_words(n, 8), (long long)quant_words(n, 4));
+      ++failures;
+    }
+    expect_ok("quant_encode int8", [&] { quant_encode(w, a, e, p8, part, st, 8, false, 1, 2, 3, 4, 0); });
+    expect_ok("quant_encode int4 stochastic, no residual", [&] { quant_encode(w, a, none, p4, part, st, 4, true, 1, 2, 3, 4, 0); });
+    expect_ok("quant_encode top words, first past 2^32", [&] {
+      quant_encode(w, a, e, p8, part, st, 8, true, top, top, top, top, (int64_t(1) << 32) + 5);
+    });
+    std::vector<at::Tensor> m8(16), m4(16);
+    for (int s = 0; s < 16; ++s) { m8[s] = T_({w8}, i32); m4[s] = T_({w4}, i32); }
+    expect_ok("quant_decode_mean M 1", [&] { quant_decode_mean({p8}, a, out, sh, 8); });
+    expect_ok("quant_decode_mean M 16", [&] { quant_decode_mean(m8, a, out, sh, 8); });
+    expect_ok("quant_decode_mean int4 M 16, no shadow", [&] { quant_decode_mean(m4, a, out, none, 4); });
+    expect_ok("quant_decode_mean M 3", [&] { quant_decode_mean({m4[0], m4[1], p4}, a, out, sh, 4); });
+    auto ws = T_({2048}, f32), as = T_({2048}, f32), ps = T_({2048 / 4 + 32}, i32), p3 = T_({6}, f64);
+    expect_ok("quant_encode small", [&] { quant_encode(ws, as, none, ps, p3, st, 8, false, 0, 0, 0, 0, 7); });
+    expect_ok("quant_decode_mean small", [&] { quant_decode_mean({ps}, as, ws, none, 8); });
+    // extents
+    auto srt = T_({n - 64}, f32), shs = T_({n - 64}, bf), p8s = T_({w8 - 1}, i32), p8l = T_({w8 + 1}, i32);
+    auto part_short = T_({3 * grid - 1}, f64), st3 = T_({3}, f64), st8 = T_({8}, f64);
+    expect_reject("quant_encode short anchor", [&] { quant_encode(w, srt, e, p8, part, st, 8, false, 1, 2, 3, 4, 0); });
+    expect_reject("quant_encode short residual", [&] { quant_encode(w, a, srt, p8, part, st, 8, false, 1, 2, 3, 4, 0); });
+    expect_reject("quant_encode short payload", [&] { quant_encode(w, a, e, p8s, part, st, 8, false, 1, 2, 3, 4, 0); });
+    expect_reject("quant_encode long payload", [&] { quant_encode(w, a, e, p8l, part, st, 8, false, 1, 2, 3, 4, 0); });
+    expect_reject("quant_encode int4 payload at int8", [&] { quant_encode(w, a, e, p4, part, st, 8, false, 1, 2, 3, 4, 0); });
+    expect_reject("quant_encode int8 payload at int4", [&] { quant_encode(w, a, e, p8, part, st, 4, false, 1, 2, 3, 4, 0); });
+    expect_reject("quant_encode short partial", [&] { quant_encode(w, a, e, p8, part_short, st, 8, false, 1, 2, 3, 4, 0); });
+    expect_reject("quant_encode short stats", [&] { quant_encode(w, a, e, p8, part, st3, 8, false, 1, 2, 3, 4, 0); });
+    expect_reject("quant_encode long stats", [&] { quant_encode(w, a, e, p8, part, st8, 8, false, 1, 2, 3, 4, 0); });
+    expect_reject("quant_decode_mean short payload", [&] { quant_decode_mean({m8[0], p8s}, a, out, sh, 8); });
+    expect_reject("quant_decode_mean short anchor", [&] { quant_decode_mean({p8}, srt, out, sh, 8); });
+    expect_reject("quant_decode_mean short shadow", [&] { quant_decode_mean({p8}, a, out, shs, 8); });
+    expect_reject("quant_decode_mean int4 payload at int8", [&] { quant_decode_mean({p4}, a, out, sh, 8); });
+    // dtypes, layout
+    auto wb = T_({n}, bf), shf = T_({n}, f32), p8f = T_({w8}, f32), partf = T_({3 * grid}, f32), stf = T_({4}, f32);
+    expect_reject("quant_encode w dtype", [&] { quant_encode(wb, a, e, p8, part, st, 8, false, 1, 2, 3, 4, 0); });
+    expect_reject("quant_encode anchor dtype", [&] { quant_encode(w, wb, e, p8, part, st, 8, false, 1, 2, 3, 4, 0); });
+    expect_reject("quant_encode residual dtype", [&] { quant_encode(w, a, wb, p8, part, st, 8, false, 1, 2, 3, 4, 0); });
+    expect_reject("quant_encode payload dtype", [&] { quant_encode(w, a, e, p8f, part, st, 8, false, 1, 2, 3, 4, 0); });
+    expect_reject("quant_encode partial dtype", [&] { quant_encode(w, a, e, p8, partf, st, 8, false, 1, 2, 3, 4, 0); });
+    expect_reject("quant_encode stats dtype", [&] { quant_encode(w, a, e, p8, part, stf, 8, false, 1, 2, 3, 4, 0); });
+    expect_reject("quant_decode_mean payload dtype", [&] { quant_decode_mean({p8f}, a, out, sh, 8); });
+    expect_reject("quant_decode_mean out dtype", [&] { quant_decode_mean({p8}, a, wb, sh, 8); });
+    expect_reject("quant_decode_mean shadow dtype", [&] { quant_decode_mean({p8}, a, out, shf, 8); });
+    auto xt = T_({2, n / 2}, f32).t();
+    expect_reject("quant_encode non-contiguous", [&] { quant_encode(xt, a, e, p8, part, st, 8, false, 1, 2, 3, 4, 0); });
+    expect_reject("quant_decode_mean non-contiguous anchor", [&] { quant_decode_mean({p8}, xt, out, sh, 8); });
+    // lengths, widths, counts, streams
+    auto w60 = T_({2044}, f32), a60 = T_({2044}, f32), w0 = T_({0}, f32), p0 = T_({0}, i32);
+    expect_reject("quant_encode numel % 64", [&] { quant_encode(w60, a60, none, ps, p3, st, 8, false, 0, 0, 0, 0, 0); });
+    expect_reject("quant_encode empty", [&] { quant_encode(w0, w0, none, p0, p3, st, 8, false, 0, 0, 0, 0, 0); });
+    expect_reject("quant_decode_mean numel % 64", [&] { quant_decode_mean({ps}, a60, w60, none, 8); });
+    expect_reject("quant_words numel % 64", [&] { quant_words(100, 8); });
+    expect_reject("quant_words bits", [&] { quant_words(128, 16); });
+    expect_reject("quant_encode bits 2", [&] { quant_encode(w, a, e, p8, part, st, 2, false, 1, 2, 3, 4, 0); });
+    expect_reject("quant_encode bits 16", [&] { quant_encode(w, a, e, p8, part, st, 16, false, 1, 2, 3, 4, 0); });
+    expect_reject("quant_decode_mean bits 0", [&] { quant_decode_mean({p8}, a, out, sh, 0); });
+    expect_reject("quant_decode_mean M 0", [&] { quant_decode_mean({}, a, out, sh, 8); });
+    std::vector<at::Tensor> m17(m8);
+    m17.push_back(p8);
+    expect_reject("quant_decode_mean M 17", [&] { quant_decode_mean(m17, a, out, sh, 8); });
+    expect_reject("quant_encode round < 0", [&] { quant_encode(w, a, e, p8, part, st, 8, true, 1, 2, -1, 4, 0); });
+    expect_reject("quant_encode client < 0", [&] { quant_encode(w, a, e, p8, part, st, 8, true, 1, 2, 3, -1, 0); });
+    expect_reject("quant_encode first < 0", [&] { quant_encode(w, a, e, p8, part, st, 8, true, 1, 2, 3, 4, -1); });
+    expect_reject("quant_encode round 2^32", [&] { quant_encode(w, a, e, p8, part, st, 8, true, 1, 2, top + 1, 4, 0); });
+    expect_reject("quant_encode seed word 2^32", [&] { quant_encode(w, a, e, p8, part, st, 8, true, top + 1, 2, 3, 4, 0); });
+    expect_reject("quant_encode first overflows", [&] {
+      quant_encode(w, a, e, p8, part, st, 8, true, 1, 2, 3, 4, std::numeric_limits<int64_t>::max() / 16);
+    });
+    // windows of one allocation
+    auto big = T_({2 * n}, f32);
+    auto lo = big.narrow(0, 0, n), mid = big.narrow(0, n / 2, n), hi = big.narrow(0, n, n);
+    expect_reject("quant_encode anchor is w", [&] { quant_encode(w, w, e, p8, part, st, 8, false, 1, 2, 3, 4, 0); });
+    expect_reject("quant_encode residual is w", [&] { quant_encode(w, a, w, p8, part, st, 8, false, 1, 2, 3, 4, 0); });
+    expect_reject("quant_encode anchor overlaps w", [&] { quant_encode(lo, mid, e, p8, part, st, 8, false, 1, 2, 3, 4, 0); });
+    expect_reject("quant_encode residual overlaps anchor", [&] { quant_encode(w, lo, mid, p8, part, st, 8, false, 1, 2, 3, 4, 0); });
+    expect_ok("quant_encode anchor beside w", [&] { quant_encode(lo, hi, e, p8, part, st, 8, false, 1, 2, 3, 4, 0); });
+    auto pv8 = big.narrow(0, n / 2, w8).view(i32);
+    expect_reject("quant_encode payload overlaps w", [&] { quant_encode(lo, a, e, pv8, part, st, 8, false, 1, 2, 3, 4, 0); });
+    expect_reject("quant_encode payload overlaps residual", [&] { quant_encode(w, a, lo, pv8, part, st, 8, false, 1, 2, 3, 4, 0); });
+    expect_reject("quant_decode_mean out is anchor", [&] { quant_decode_mean({p8}, a, a, sh, 8); });
+    expect_reject("quant_decode_mean out overlaps anchor", [&] { quant_decode_mean({p8}, mid, lo, sh, 8); });
+    expect_ok("quant_decode_mean out beside anchor", [&] { quant_decode_mean({p8}, hi, lo, sh, 8); });
+    expect_reject("quant_decode_mean out overlaps a payload", [&] { quant_decode_mean({m8[0], pv8}, a, lo, sh, 8); });
+    auto shv = big.narrow(0, n / 2, n / 2).view(bf);
+    expect_reject("quant_decode_mean shadow overlaps out", [&] { quant_decode_mean({p8}, a, lo, shv, 8); });
+    expect_reject("quant_decode_mean shadow overlaps anchor", [&] { quant_decode_mean({p8}, lo, out, shv, 8); });
+    expect_reject("quant_decode_mean shadow overlaps a payload", [&] { quant_decode_mean({pv8}, a, out, shv, 8); });
   }
   // ---- embedding backward (work = pieces + LayerNorm partials)
   {

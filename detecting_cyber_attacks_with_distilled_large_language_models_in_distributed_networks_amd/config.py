@@ -86,6 +86,12 @@ class FedConfig:
     privacy_noise: float = 0.0              # z, the noise multiplier: the sum carries std z * C
     privacy_delta: float = 1e-5             # the delta of the reported (epsilon, delta)
     privacy_seed: Optional[int] = None      # None: 64 bits of os.urandom per process; an int: fixed (tests)
+    # Quantized update exchange (parallel/compress.py; QSGD, Alistarh et al. 2017; error feedback,
+    # Karimireddy et al. 2019): a client sends w - w_global as int8 / int4 codes with one fp32 scale per 64
+    # elements, and keeps what the rounding lost for its next update.  "none": the fp32 exchange (reference)
+    compress: str = "none"                  # "none" | "int8" | "int4"
+    compress_error_feedback: bool = True    # carry the quantization error into the next round's update
+    compress_rounding: str = "nearest"      # "nearest" | "stochastic" (unbiased; Philox keyed by base_seed)
     participation: float = 1.0              # fraction of clients aggregated per round
     timeout_s: float = 300.0                # server.py:10 / client1.py:22
     heartbeat_s: float = 1.0                # failure detection (parallel/health.py); 0 disables

@@ -17,6 +17,7 @@ client does the client's file output).
 from __future__ import annotations
 
 import json
+import math
 import os
 import time
 from typing import Dict, List, Optional
@@ -29,6 +30,7 @@ from ..engine import ArenaAdam, evaluate_model, train_model
 from ..models import DDoSClassifier, DistilBertConfig
 from ..parallel import comm, health
 from ..parallel.dp import DPShardLoader, GradSync, dp_seed_offset, make_topology
+from ..parallel.compress import check_compress_config, make_compressor
 from ..parallel.fedavg import broadcast_model, fedavg_
 from ..parallel.privacy import check_privacy_config, make_privatizer
 from ..parallel.robust import check_robust_config, make_robust, most_trimmed, robust_aggregate_
@@ -111,6 +113,7 @@ class FederatedClient:
         check_server_config(cfg)  # (an unknown kind, a bad value, or transport=tcp: refused before any work)
         check_robust_config(cfg)  # (likewise: an unknown aggregator, tcp, weighted_fedavg)
         check_privacy_config(cfg, self.topo.gpus_per_client)  # (a bad clip / noise / delta, weighted_fedavg, replicas)
+        check_compress_config(cfg, self.topo.gpus_per_client)  # (an unknown width, tcp, a robust aggregator, ...)
         log.phase("Starting client")
         with self.timer("preprocess"):
             if self.frame is None:
@@ -188,15 +191,22 @@ class FederatedClient:
                      + (f" (trim_ratio {self.robust.trim_ratio:g})" if self.robust.aggregator == "trimmed_mean" else ""))
         # Client-level differential privacy (parallel/privacy.py; None: privacy_clip == 0, today's path)
         self.privacy = make_privatizer(cfg, self.topo.gpus_per_client)
-        self._privacy_anchor = None
         if self.privacy is not None:
             log.info(_privacy_line(self.privacy, cfg.rounds))
+        # Quantized update exchange (parallel/compress.py; None: compress == "none", today's path)
+        self.compress = make_compressor(cfg, self.topo.gpus_per_client)
+        if self.compress is not None:
+            log.info(_compress_line(self.compress))
+        self._round_anchor = None  # the round's starting weights: what privacy and compression measure against
         self.health = None
         if self.di.distributed and cfg.heartbeat_s > 0 and cfg.transport != "tcp":
             self.health = health.start(cfg.heartbeat_s, cfg.heartbeat_stale_s, cfg.timeout_s)
         restarts = int(os.environ.get("TORCHELASTIC_RESTART_COUNT", "0"))
         if restarts:
             log.info(f"elastic restart #{restarts}: resuming at round {self.start_round + 1}")
+            if self.compress is not None and self.compress.error_feedback:
+                self.compress.reset()
+                log.info("quantization residual lost with the restarted process: error feedback starts again from zero")
         log.info(f"data: {len(self.data.train)} train / {len(self.data.val)} val / {len(self.data.test)} test rows "
                  f"(sampled {self.data.n_rows}), impl={self.model.impl}, device={dev}")
         return self
@@ -285,12 +295,12 @@ class FederatedClient:
         log.phase(f"Starting round {r + 1}/{cfg.rounds}")
         opt = make_optimizer(model, cfg, r, cfg.rounds, cfg.epochs * len(self.train_loader))
         opt.reset_state()  # a fresh Adam every round (client1.py:380), "has state" row flags included
-        if self.privacy is not None:
-            # the round's starting weights: what the update is measured (and clipped) against
-            if self._privacy_anchor is None:
-                self._privacy_anchor = torch.empty_like(model.arena.master)
+        if self.privacy is not None or self.compress is not None:
+            # the round's starting weights: what the update is measured (clipped, quantized) against
+            if self._round_anchor is None:
+                self._round_anchor = torch.empty_like(model.arena.master)
             with torch.no_grad():
-                self._privacy_anchor.copy_(model.arena.master)
+                self._round_anchor.copy_(model.arena.master)
         opt_path = os.path.join(cfg.out_dir, f"client{self.client_id}_optim.pth")
         if cfg.save_optimizer and r == self.start_round:
             ck.load_optimizer(opt, opt_path)
@@ -343,7 +353,7 @@ class FederatedClient:
             # what is sent is the privatized copy (the local metrics and clientN_model.pth above describe
             # the trained weights); privatize, then poison: a liar lies whatever the protocol
             A = model.arena
-            priv = self.privacy.privatize_(A.master, self._privacy_anchor, self.idx, r, len(part), shadow=A.shadow,
+            priv = self.privacy.privatize_(A.master, self._round_anchor, self.idx, r, len(part), shadow=A.shadow,
                                            arena=A)
             if A.shadow is not None:
                 model.mark_shadow_synced()
@@ -371,6 +381,10 @@ class FederatedClient:
             elif self.robust is not None:
                 total_w = fedavg_(model, participate=contributes, comm=self.comm, server=self.server,
                                   robust=self.robust)
+            elif self.compress is not None:
+                # privatize, then poison, then encode: quantizing a privatized update is post-processing
+                total_w = fedavg_(model, participate=contributes, comm=self.comm, server=self.server,
+                                  compress=self.compress, anchor=self._round_anchor, client=self.idx, round=r)
             else:
                 total_w = fedavg_(model, weight=weight, participate=contributes, comm=self.comm, server=self.server)
             if model.device.type == "cuda":
@@ -385,6 +399,9 @@ class FederatedClient:
         trim = self.robust.last if self.robust is not None and total_w > 0 else None
         if trim is not None:
             log.info(_trim_line(trim))
+        comp = _compress_fields(self.compress.last) if self.compress is not None and self.compress.last else None
+        if comp is not None:
+            log.info(_compress_sent_line(comp))
         if self.di.is_main and cfg.save_checkpoints:
             # weights, the server optimizer's moments, then the round tag (_resume)
             ck.save_global(model, cfg.out_dir, r + 1, server=self.server)
@@ -413,6 +430,8 @@ class FederatedClient:
             rec.update(delta_l2=norms["delta_l2"], step_l2=norms["step_l2"])
         if trim is not None:
             rec.update(trimmed_share=trim["trimmed_share"], k=trim["k"])
+        if comp is not None:  # (after the trim keys, before privacy's: update_l2 is privacy's when both are on)
+            rec.update(comp)
         if priv is not None:
             rec.update(priv)
         elif self.privacy is not None:  # (not sampled this round: nothing of this client was released)
@@ -502,6 +521,25 @@ def _privacy_fields(rep: Dict, privacy, rounds_done: int) -> Dict:
     """A record's privacy keys from ``Privatizer.privatize_``'s report."""
     return {"update_l2": rep["update_l2"], "clipped": rep["clipped"], "privacy_sigma": rep["sigma"],
             "privacy_epsilon": privacy.epsilon(rounds_done)}
+
+
+def _compress_line(compress) -> str:
+    """One log line for a job with the quantized exchange."""
+    from ..parallel.compress import payload_ratio
+    return (f"quantized update exchange: int{compress.bits}, {compress.rounding} rounding, error feedback "
+            f"{'on' if compress.error_feedback else 'off'} (payload {payload_ratio(compress.bits):.2f}x smaller than fp32)")
+
+
+def _compress_fields(rep: Dict) -> Dict:
+    """A record's compression keys from ``Compressor.encode_``'s report."""
+    return {"compress_ratio": rep["ratio"], "payload_bytes": rep["payload_bytes"], "update_l2": rep["update_l2"],
+            "quant_error_l2": rep["error_l2"], "bad_groups": rep["bad_groups"]}
+
+
+def _compress_sent_line(comp: Dict) -> str:
+    return (f"quantized update: {comp['payload_bytes']} B sent ({comp['compress_ratio']:.2f}x smaller), |update| = "
+            f"{comp['update_l2']:.6g}, |quantization error| = {comp['quant_error_l2']:.6g}"
+            + (f", [WARN] {comp['bad_groups']} group(s) with inf / NaN sent as zero" if comp["bad_groups"] else ""))
 
 
 def _trim_line(trim: Dict) -> str:
@@ -604,6 +642,13 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
     ``clipped`` / ``privacy_sigma`` / ``privacy_epsilon``, the round record ``privacy_epsilon``
     (tests/test_privacy_cpu.py: equal to the 2-rank gloo run bit for bit under a fixed seed).
 
+    With the quantized exchange (``cfg.compress``, parallel/compress.py) every client's copy -- after
+    privacy and poisoning -- is encoded against the round's start with the client's own residual (the
+    job's ``client.compress`` keeps one per virtual client), and ``decode_mean_`` of the payloads takes the
+    place of ``_average_masters``: the calls ``fedavg_(..., compress=)`` makes.  Each client record carries
+    ``compress_ratio`` / ``payload_bytes`` / ``update_l2`` / ``quant_error_l2`` / ``bad_groups``
+    (tests/test_compress_cpu.py: equal to the 2-rank gloo run bit for bit).
+
     Returns ``rounds`` (one record per round: per-client local / aggregated metrics, the pooled
     aggregated confusion, the FedAvg time) plus the LAST round's ``clients`` /
     ``aggregated_confusion`` / ``fedavg_ms`` at the top level (the 1-round API of earlier rounds).
@@ -630,6 +675,10 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
     robust = make_robust(cfg)  # (None: the plain mean -- _average_masters, untouched)
     # the job's Privatizer (None: privacy_clip == 0) -- one object, so one seed, for every virtual client
     privacy = getattr(client, "privacy", None)
+    # the job's Compressor (None: compress == "none") -- it keeps one residual per virtual client
+    compress = getattr(client, "compress", None)
+    if compress is not None and robust is not None:
+        raise ValueError("compress needs aggregator='mean'")
     t_init = teacher.arena.master.detach().clone() if teacher is not None else None
     say = progress or (lambda msg: None)
     # per-client state that survives the rounds (a real client's process keeps it)
@@ -644,7 +693,7 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
                    "rng": model.rng.detach().clone(), "torch_counter": model.torch_counter, "teacher": None})
     hist = []
     for r in range(rounds):
-        locals_, recs = [], []
+        locals_, recs, payloads = [], [], []
         for v, c in enumerate(cs):
             data, loader, test = c["data"], c["loader"], c["test"]
             rec = {"client": v + 1, "round": r + 1, "train_rows": len(data.train), "test_rows": len(data.test)}
@@ -687,6 +736,10 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
                 rec.update(_privacy_fields(privacy.privatize_(locals_[-1], glob, v, r, n_clients, arena=A), privacy,
                                            r + 1))
             faults.poison_(locals_[-1], cfg, v, r)  # (a lying client: what it sends, not what it evaluated)
+            if compress is not None:  # (what leaves the client: codes and scales of its update + residual)
+                payloads.append(compress.encode_(locals_[-1], glob, v, r))
+                for key, val in _compress_fields(compress.last).items():
+                    rec.setdefault(key, val)  # (update_l2 stays privacy's when both are on)
             rec.update({"train": tr, "train_wall_s": time.perf_counter() - t0, "local_test": local})
             # client drift: how far the local epochs moved this client from the round's start
             rec["l2_local_to_start"] = float((locals_[-1] - glob).norm())
@@ -699,6 +752,10 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
         if robust is not None:
             trim = robust_aggregate_(model, locals_, robust.k(len(locals_)), server)
             norms = server.last if server is not None else None
+        elif compress is not None:
+            compress.decode_mean_(model, payloads, glob, server)
+            norms = server.last if server is not None else None
+            del payloads
         elif server is None:
             _average_masters(model, locals_)
         else:
@@ -722,6 +779,14 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
             hist[-1].update(trimmed_share=trim["trimmed_share"], k=trim["k"])
             client.log.info(_trim_line(trim))
             say(f"round {r + 1}/{rounds} " + _trim_line(trim))
+        if compress is not None:
+            up = math.sqrt(sum(c["update_l2"] ** 2 for c in recs)) if privacy is None else None
+            er = math.sqrt(sum(c["quant_error_l2"] ** 2 for c in recs))
+            hist[-1].update(compress_ratio=recs[0]["compress_ratio"], payload_bytes=recs[0]["payload_bytes"],
+                            quant_error_l2=er, bad_groups=sum(c["bad_groups"] for c in recs))
+            say(f"round {r + 1}/{rounds} quantized exchange: int{compress.bits}, {recs[0]['payload_bytes']} B per client "
+                f"({recs[0]['compress_ratio']:.2f}x smaller), pooled |quantization error| = {er:.6g}"
+                + (f" of |update| = {up:.6g}" if up is not None else ""))
         if privacy is not None:
             hist[-1].update(privacy_epsilon=privacy.epsilon(r + 1))
             say(f"round {r + 1}/{rounds} privacy: epsilon <= {hist[-1]['privacy_epsilon']:.6g} at delta "

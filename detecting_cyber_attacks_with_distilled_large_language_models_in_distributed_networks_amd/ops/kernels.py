@@ -1205,3 +1205,39 @@ def privacy_gauss(out, seed, round, client, first4=0):
     (``parallel.privacy.torch_gauss`` is its fp64 host mirror)."""
     lo, hi = _seed_words(seed)
     ext().privacy_gauss(out, lo, hi, int(round), int(client), int(first4))
+
+
+QUANT_MAX_CLIENTS = 16
+QUANT_GROUP = 64  # elements per fp32 scale
+
+
+def quant_grid(n):
+    """Blocks of a ``quant_encode`` / ``quant_decode_mean`` launch over ``n`` floats (encode's
+    ``partial`` holds three doubles per block)."""
+    return int(ext().quant_grid(int(n)))
+
+
+def quant_words(n, bits):
+    """int32 words of the payload of ``n`` floats (``n % 64 == 0``) at ``bits`` (8 or 4):
+    ``n * bits / 32`` of codes, then ``n / 64`` of fp32 scale bit patterns."""
+    return int(ext().quant_words(int(n), int(bits)))
+
+
+def quant_encode(w, anchor, residual, payload, partial, stats, bits, stochastic, seed, round, client, first=0):
+    """``payload`` (int32, ``quant_words(n, bits)``) = the codes and per-64 scales of ``v = (w - anchor)
+    + residual`` in one pass plus a one-block finalize (compress.hip; ``parallel.compress.torch_quantize_``
+    is the specification); ``residual`` (optional) becomes the quantization error ``v - s q`` in place.
+    ``stats`` (float64, 4) = [|v|, |e'|, bad groups, 0]; ``partial`` (float64, >= 3 * ``quant_grid(n)``,
+    every entry written).  ``stochastic``: element i rounds with the Philox word of global index
+    ``64 * first + i`` of the stream (seed, round, client); otherwise to nearest."""
+    lo, hi = _seed_words(seed)
+    ext().quant_encode(w, anchor, residual, payload, partial, stats, int(bits), bool(stochastic), lo, hi, int(round),
+                       int(client), int(first))
+
+
+def quant_decode_mean(payloads, anchor, out, shadow=None, bits=8):
+    """``out = anchor + mean`` of the M = len(payloads) decoded payloads (1 <= M <= 16, summed in the
+    given order, then times ``float32(1 / M)``), ``shadow`` (optional) = bf16(out), in one pass
+    (``parallel.compress.torch_decode_mean_`` is the specification).  ``out`` / ``shadow`` overlap no
+    input."""
+    ext().quant_decode_mean(list(payloads), anchor, out, shadow, int(bits))
