@@ -73,6 +73,77 @@ def attention_ref(qkv: torch.Tensor, mask: torch.Tensor, B: int, S: int, H: int,
     return ctx, lse
 
 
+BF16_U = 2.0 ** -8  # bf16 unit roundoff (8 significand bits, round to nearest)
+
+
+def attention_oracle(qkv: torch.Tensor, mask: torch.Tensor, B: int, S: int, H: int, p: float = 0.0, counter=None,
+                     site: int = 0, dctx: Optional[torch.Tensor] = None) -> dict:
+    """float64 attention with the absolute-weighted sums that bound a correct bf16 kernel's error.
+
+    qkv [B*S, 3*H*64]; mask [B, S], any 0/1 pattern with a live key in every row; dropout as in
+    ``attention_ref`` (flat index ((b H + h) S + q) S + k).  With P = softmax(q k^T / 8 + mask),
+    keep the dropout bits, Pd = keep P / (1 - p) and dO = dctx, returns a dict of float64 tensors:
+
+      ctx [B*S, D], lse [B, H, S], A = Pd |V| (like ctx)
+      with dctx: dqkv [B*S, 3D] from the explicit formulas
+          dP = dO V^T, dPd = keep dP / (1 - p), delta = rowsum(dO * ctx), dS = P * (dPd - delta),
+          dQ = dS K / 8, dK = dS^T Q / 8, dV = Pd^T dO
+        Dh [B, H, S] = rowsum(|dO| * A), W [B, H, S, S] = |dS| + Dh P, and
+        E [B*S, 3D] = (W |K| / 8 | W^T |Q| / 8 | Pd^T |dO|), laid out like dqkv.
+
+    The kernels round Pd (or dS) to bf16 once and the output once: at most 2 u A on ctx and
+    2 u E_dV on dV (u = ``BF16_U``).  delta is formed from the bf16 ctx (error <= 2 u A), so
+    |d delta| <= 2 u Dh, which with the dS and output roundings gives 2 u E on dQ / dK.  fp32
+    accumulation, exp and lse are below 2^-15 of the same sums (``attention_bound_ratio``).
+    """
+    D = H * 64
+    x = qkv.to(torch.float64).view(B, S, 3, H, 64).permute(2, 0, 3, 1, 4)  # each [B, H, S, 64]
+    q, k, v = x[0], x[1], x[2]
+    live = (mask.view(B, 1, 1, S) != 0)
+    scores = (q @ k.transpose(-1, -2)) * 0.125
+    scores = scores.masked_fill(~live, float("-inf"))
+    lse = torch.logsumexp(scores, dim=-1)
+    P = torch.exp(scores - lse.unsqueeze(-1))
+    if p > 0.0 and counter is not None:
+        keep = keep_mask(counter, site, P.numel(), p, device=P.device).view(P.shape).to(torch.float64) / (1.0 - p)
+    else:
+        keep = torch.ones_like(P)
+    Pd = P * keep
+
+    def rows(t):  # [B, H, S, 64] -> [B*S, D]
+        return t.permute(0, 2, 1, 3).reshape(B * S, D)
+
+    ctx = Pd @ v
+    A = Pd @ v.abs()
+    out = {"ctx": rows(ctx), "lse": lse, "A": rows(A)}
+    if dctx is None:
+        return out
+    dO = dctx.to(torch.float64).view(B, S, H, 64).permute(0, 2, 1, 3)
+    dPd = (dO @ v.transpose(-1, -2)) * keep
+    delta = (dO * ctx).sum(-1, keepdim=True)
+    dS = P * (dPd - delta)
+    Dh = (dO.abs() * A).sum(-1)
+    W = dS.abs() + Dh.unsqueeze(-1) * P
+    out["dqkv"] = torch.cat([rows(dS @ k * 0.125), rows(dS.transpose(-1, -2) @ q * 0.125),
+                             rows(Pd.transpose(-1, -2) @ dO)], dim=1)
+    out["Dh"], out["W"] = Dh, W
+    out["E"] = torch.cat([rows(W @ k.abs() * 0.125), rows(W.transpose(-1, -2) @ q.abs() * 0.125),
+                          rows(Pd.transpose(-1, -2) @ dO.abs())], dim=1)
+    return out
+
+
+def attention_bound_ratio(got: torch.Tensor, want: torch.Tensor, E: torch.Tensor) -> float:
+    """max |got - want| / (2.5 u E + 1e-30) over the elements: <= 1 for a correct kernel.  2.5 is the
+    derived 2 (``attention_oracle``) plus a quarter for the fp32 terms; 1e-30 is an absolute floor for
+    fp32 / bf16 underflow, far above 512 denormal terms and far below any value the tests produce.
+    Where E is exactly 0 (dK / dV of a masked key) ``got`` must be exactly 0: any other value gives a
+    ratio above 1e20.  A non-finite ``got`` gives inf."""
+    err = (got.to(torch.float64) - want.to(torch.float64)).abs()
+    ratio = err / (2.5 * BF16_U * E.to(torch.float64) + 1e-30)
+    ratio = torch.where(torch.isfinite(ratio), ratio, torch.full_like(ratio, float("inf")))
+    return ratio.max().item() if ratio.numel() else 0.0
+
+
 def head_ref(hidden: torch.Tensor, B: int, S: int, W, b, p=0.3, counter=None, site=0):
     """hidden [B*S, D] -> logits [B, 2] via CLS -> Dropout -> Linear."""
     D = hidden.shape[-1]

@@ -232,7 +232,8 @@ def test_attention_fwd(B, S, p):
     assert (lse - rlse).abs().max().item() < 1e-3
 
 
-@pytest.mark.parametrize("B,S,p", [(2, 128, 0.0), (2, 128, 0.1), (1, 256, 0.1), (2, 512, 0.1), (1, 512, 0.0)])
+@pytest.mark.parametrize("B,S,p", [(2, 128, 0.0), (2, 128, 0.1), (1, 256, 0.1), (2, 512, 0.1), (1, 512, 0.0),
+                                   (1, 64, 0.0), (2, 64, 0.1)])
 def test_attention_bwd(B, S, p):
     H = 12
     qkv = bf(B * S, 3 * H * 64, seed=15)
