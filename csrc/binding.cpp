@@ -168,6 +168,13 @@ int fd_quant_encode(const float* w, const float* anchor, float* residual, int32_
                     long long client, long long first, long long n, hipStream_t st);
 int fd_quant_decode_mean(const int32_t* const* src, int M, const float* anchor, float* out, void* shadow, int bits,
                          long long n, hipStream_t st);
+int fd_topk_grid(long long n);
+long long fd_topk_words(long long n, long long k);
+long long fd_topk_work_bytes(long long n);
+int fd_topk_encode(const float* w, const float* anchor, float* residual, int32_t* payload, void* work, double* stats,
+                   long long k, long long n, hipStream_t st);
+int fd_topk_decode_mean(const int32_t* const* src, int M, const float* anchor, float* out, void* shadow, long long k,
+                        long long n, hipStream_t st);
 }
 
 namespace {
@@ -2069,6 +2076,93 @@ void quant_decode_mean(const std::vector<at::Tensor>& payloads, const at::Tensor
            "quant_decode_mean");
 }
 
+// Top-k sparsified update exchange (sparsify.hip).  A payload of n floats with k entries is one int32
+// tensor: ceil(n / 4096) + 1 offsets, k fp32 bit patterns, ceil(k / 2) words of uint16 local indices.
+int64_t topk_grid(int64_t n) { return (int64_t)fd_topk_grid(n); }
+
+int64_t topk_words(int64_t n, int64_t k) {
+  TORCH_CHECK(n > 0 && n % 64 == 0 && n <= 0x7fffffc0ll, "topk_words: numel % 64 and below 2^31, got ", n);
+  TORCH_CHECK(k >= 1 && k <= n / 2, "topk_words: 1 <= k <= numel / 2, got k = ", k, " for ", n, " elements");
+  return (int64_t)fd_topk_words(n, k);
+}
+
+int64_t topk_work_bytes(int64_t n) {
+  TORCH_CHECK(n > 0 && n % 64 == 0 && n <= 0x7fffffc0ll, "topk_work_bytes: numel % 64 and below 2^31, got ", n);
+  return (int64_t)fd_topk_work_bytes(n);
+}
+
+// payload = the k largest-magnitude entries of v = (w - anchor) + residual; residual (optional) = what
+// was not sent, in place; stats (float64, 8) = {|v|, |e'|, bad elements, sent, threshold, 0, 0, 0}; work
+// (uint8, >= topk_work_bytes(n), 16-byte aligned) is scratch.  Nothing is launched unless every check
+// passes; no two of w, anchor, residual, payload, work, stats overlap.
+void topk_encode(const at::Tensor& w, const at::Tensor& anchor, const c10::optional<at::Tensor>& residual,
+                 const at::Tensor& payload, const at::Tensor& work, const at::Tensor& stats, int64_t k) {
+  need(w, at::kFloat, "w");
+  need(anchor, at::kFloat, "anchor");
+  need_opt(residual, at::kFloat, "residual");
+  need(payload, at::kInt, "payload");
+  need(work, at::kByte, "work");
+  need(stats, at::kDouble, "stats");
+  const bool has_res = residual.has_value() && residual->defined();
+  const int64_t n = w.numel();
+  const int64_t words = topk_words(n, k);
+  TORCH_CHECK(anchor.numel() == n, "topk_encode: anchor has ", anchor.numel(), " elements, w ", n);
+  if (has_res) TORCH_CHECK(residual->numel() == n, "topk_encode: residual has ", residual->numel(), " elements, w ", n);
+  TORCH_CHECK(payload.numel() == words, "topk_encode: payload has ", payload.numel(), " words, expected ", words);
+  const auto dev = w.device();
+  TORCH_CHECK(anchor.device() == dev && payload.device() == dev && work.device() == dev && stats.device() == dev &&
+                  (!has_res || residual->device() == dev),
+              "topk_encode: tensors on one device");
+  TORCH_CHECK(work.numel() >= (int64_t)fd_topk_work_bytes(n), "topk_encode: work has ", work.numel(), " bytes, needs ",
+              (int64_t)fd_topk_work_bytes(n));
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(work.data_ptr()) % 16 == 0, "topk_encode: work must be 16-byte aligned");
+  TORCH_CHECK(stats.numel() == 8, "topk_encode: stats holds 8 doubles");
+  std::vector<const at::Tensor*> bufs = {&w, &anchor, &payload, &work, &stats};
+  if (has_res) bufs.push_back(&*residual);
+  for (size_t i = 0; i < bufs.size(); ++i)
+    for (size_t j = i + 1; j < bufs.size(); ++j)
+      TORCH_CHECK(!privacy_overlap(*bufs[i], *bufs[j]), "topk_encode: buffers ", i, " and ", j, " overlap");
+  check_rc(fd_topk_encode(w.data_ptr<float>(), anchor.data_ptr<float>(), ptr<float>(residual),
+                          payload.data_ptr<int32_t>(), work.data_ptr(), stats.data_ptr<double>(), k, n, stream()),
+           "topk_encode");
+}
+
+// out = anchor + the mean of the M scattered payloads (1 <= M <= 16, added in the given order), shadow
+// (optional) = bf16(out).  out and shadow overlap no input.
+void topk_decode_mean(const std::vector<at::Tensor>& payloads, const at::Tensor& anchor, const at::Tensor& out,
+                      const c10::optional<at::Tensor>& shadow, int64_t k) {
+  const int64_t M = (int64_t)payloads.size();
+  TORCH_CHECK(M >= 1 && M <= 16, "topk_decode_mean: 1 <= M <= 16 payloads, got ", M);
+  need(anchor, at::kFloat, "anchor");
+  need(out, at::kFloat, "out");
+  need_opt(shadow, at::kBFloat16, "shadow");
+  const bool has_shadow = shadow.has_value() && shadow->defined();
+  const int64_t n = out.numel();
+  const int64_t words = topk_words(n, k);
+  TORCH_CHECK(anchor.numel() == n, "topk_decode_mean: anchor has ", anchor.numel(), " elements, out ", n);
+  if (has_shadow) TORCH_CHECK(shadow->numel() == n, "topk_decode_mean: shadow size");
+  const auto dev = out.device();
+  TORCH_CHECK(anchor.device() == dev && (!has_shadow || shadow->device() == dev),
+              "topk_decode_mean: tensors on one device");
+  TORCH_CHECK(!privacy_overlap(out, anchor), "topk_decode_mean: out overlaps anchor");
+  if (has_shadow)
+    TORCH_CHECK(!privacy_overlap(*shadow, out) && !privacy_overlap(*shadow, anchor),
+                "topk_decode_mean: shadow overlaps out or anchor");
+  const int32_t* ptrs[16];
+  for (int64_t s = 0; s < M; ++s) {
+    need(payloads[s], at::kInt, "payload");
+    TORCH_CHECK(payloads[s].device() == dev, "topk_decode_mean: tensors on one device");
+    TORCH_CHECK(payloads[s].numel() == words, "topk_decode_mean: payload ", s, " has ", payloads[s].numel(),
+                " words, expected ", words);
+    TORCH_CHECK(!privacy_overlap(payloads[s], out) && (!has_shadow || !privacy_overlap(payloads[s], *shadow)),
+                "topk_decode_mean: an output overlaps payload ", s);
+    ptrs[s] = payloads[s].data_ptr<int32_t>();
+  }
+  check_rc(fd_topk_decode_mean(ptrs, (int)M, anchor.data_ptr<float>(), out.data_ptr<float>(), ptr<void>(shadow), k, n,
+                               stream()),
+           "topk_decode_mean");
+}
+
 }  // namespace
 
 #ifndef FD_HOST_VALIDATION
@@ -2206,5 +2300,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("seed_hi"), py::arg("round"), py::arg("client"), py::arg("first") = 0);
   m.def("quant_decode_mean", &quant_decode_mean, py::arg("payloads"), py::arg("anchor"), py::arg("out"),
         py::arg("shadow") = py::none(), py::arg("bits") = 8);
+  m.def("topk_grid", &topk_grid);
+  m.def("topk_words", &topk_words);
+  m.def("topk_work_bytes", &topk_work_bytes);
+  m.def("topk_encode", &topk_encode, py::arg("w"), py::arg("anchor"), py::arg("residual"), py::arg("payload"),
+        py::arg("work"), py::arg("stats"), py::arg("k"));
+  m.def("topk_decode_mean", &topk_decode_mean, py::arg("payloads"), py::arg("anchor"), py::arg("out"),
+        py::arg("shadow") = py::none(), py::arg("k") = 1);
 }
 #endif  // FD_HOST_VALIDATION

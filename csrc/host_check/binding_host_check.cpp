@@ -824,6 +824,82 @@ int fd_quant_decode_mean(const int32_t* const* src, int M, const float* anchor, 
   }
   return 0;
 }
+// (csrc/kernels/sparsify.hip: chunks of 4096 elements, at most 1024 blocks, the layout of `work`)
+namespace {
+bool hc_topk_n_ok(long long n) { return n > 0 && n % 64 == 0 && n <= 0x7fffffc0ll; }
+long long hc_topk_chunks(long long n) { return (n + 4095) / 4096; }
+}  // namespace
+int fd_topk_grid(long long n) { return hc_topk_n_ok(n) ? (int)std::min<long long>(hc_topk_chunks(n), 1024) : 0; }
+long long fd_topk_words(long long n, long long k) {
+  if (!hc_topk_n_ok(n) || k < 1 || k > n / 2) return 0;
+  return hc_topk_chunks(n) + 1 + k + (k + 1) / 2;
+}
+long long fd_topk_work_bytes(long long n) {
+  if (!hc_topk_n_ok(n)) return 0;
+  return n * 4 + (2048 + 1024 + 1024 + 16) * 4ll + hc_topk_chunks(n) * 16 + fd_topk_grid(n) * 16ll;
+}
+int fd_topk_encode(const float* w, const float* anchor, float* residual, int32_t* payload, void* work, double* stats,
+                   long long k, long long n, hipStream_t) {
+  ++hc::calls;
+  // the kernels read n / 4 float4 of w, anchor (and residual, which they also write), write
+  // fd_topk_words int32 of payload (the index halves as uint16: 2 * ceil(k / 2) of them), use
+  // fd_topk_work_bytes of work from a 16-byte aligned base, and the finalize writes eight doubles of stats
+  if (!hc_topk_n_ok(n)) {
+    hc::violations.push_back("topk_encode: n % 64 / n < 2^31");
+    return 0;
+  }
+  if (k < 1 || k > n / 2) {
+    hc::violations.push_back("topk_encode: k");
+    return 0;
+  }
+  const long long words = fd_topk_words(n, k), wbytes = fd_topk_work_bytes(n);
+  hc::span(w, n * 4, "topk_encode w");
+  hc::span(anchor, n * 4, "topk_encode anchor");
+  hc::opt_span(residual, n * 4, "topk_encode residual");
+  hc::span(payload, words * 4, "topk_encode payload");
+  hc::span(work, wbytes, "topk_encode work");
+  hc::span(stats, 64, "topk_encode stats");
+  if (((uintptr_t)work & 15u) != 0) hc::violations.push_back("topk_encode: work alignment");
+  const void* bufs[6] = {w, anchor, residual, payload, work, stats};
+  const long long bytes[6] = {n * 4, n * 4, n * 4, words * 4, wbytes, 64};
+  for (int i = 0; i < 6; ++i)
+    for (int j = i + 1; j < 6; ++j)
+      if (bufs[i] && bufs[j] && hc_overlaps(bufs[i], bytes[i], bufs[j], bytes[j]))
+        hc::violations.push_back("topk_encode: buffers overlap");
+  return 0;
+}
+int fd_topk_decode_mean(const int32_t* const* src, int M, const float* anchor, float* out, void* shadow, long long k,
+                        long long n, hipStream_t) {
+  ++hc::calls;
+  // the kernel reads, of each of the M payloads, the C + 1 offsets and -- whatever they hold -- entries
+  // in [0, k) only: k value words and ceil(k / 2) index words; n / 4 float4 of anchor; it writes as many
+  // float4 to out (and uint2 to the shadow)
+  if (!hc_topk_n_ok(n)) {
+    hc::violations.push_back("topk_decode_mean: n % 64 / n < 2^31");
+    return 0;
+  }
+  if (M < 1 || M > 16 || k < 1 || k > n / 2) {
+    hc::violations.push_back("topk_decode_mean: M / k");
+    return 0;
+  }
+  const long long words = fd_topk_words(n, k);
+  hc::span(anchor, n * 4, "topk_decode_mean anchor");
+  hc::span(out, n * 4, "topk_decode_mean out");
+  hc::opt_span(shadow, n * 2, "topk_decode_mean shadow");
+  if (anchor && out && hc_overlaps(anchor, n * 4, out, n * 4)) hc::violations.push_back("topk_decode_mean: out overlaps anchor");
+  if (shadow && ((out && hc_overlaps(shadow, n * 2, out, n * 4)) || (anchor && hc_overlaps(shadow, n * 2, anchor, n * 4))))
+    hc::violations.push_back("topk_decode_mean: shadow overlaps out or anchor");
+  if (!src) {
+    hc::violations.push_back("topk_decode_mean: no payloads");
+    return 0;
+  }
+  for (int s = 0; s < M; ++s) {
+    hc::span(src[s], words * 4, "topk_decode_mean payload");
+    if (src[s] && ((out && hc_overlaps(src[s], words * 4, out, n * 4)) || (shadow && hc_overlaps(src[s], words * 4, shadow, n * 2))))
+      hc::violations.push_back("topk_decode_mean: an output overlaps a payload");
+  }
+  return 0;
+}
 }  // extern "C"
 
 // ------------------------------------------------------------------ driver
@@ -1629,6 +1705,109 @@ int main() {
     expect_reject("quant_decode_mean shadow overlaps out", [&] { quant_decode_mean({p8}, a, lo, shv, 8); });
     expect_reject("quant_decode_mean shadow overlaps anchor", [&] { quant_decode_mean({p8}, lo, out, shv, 8); });
     expect_reject("quant_decode_mean shadow overlaps a payload", [&] { quant_decode_mean({pv8}, a, out, shv, 8); });
+  }
+  // ---- top-k sparsified exchange: w / anchor / residual fp32, the int32 payload, the byte workspace
+  {
+    const auto f64 = at::kDouble, u8 = at::kByte;
+    const int64_t n = 4096 * 1024 + 3 * 4096 + 64 * 5;  // the chunk loops wrap, ragged last chunk
+    const int64_t k = n / 100, kh = n / 2;
+    const int64_t wk = fd_topk_words(n, k), w1 = fd_topk_words(n, 1), wh = fd_topk_words(n, kh), wb = fd_topk_work_bytes(n);
+    auto w = T_({n}, f32), a = T_({n}, f32), e = T_({n}, f32), sh = T_({n}, bf), out = T_({n}, f32);
+    auto pk = T_({wk}, i32), p1 = T_({w1}, i32), ph = T_({wh}, i32), work = T_({wb}, u8), st = T_({8}, f64);
+    if (topk_words(n, k) != (n + 4095) / 4096 + 1 + k + (k + 1) / 2 || topk_words(64, 1) != 4 || topk_grid(n) != 1024 ||
+        topk_grid(64) != 1 || topk_work_bytes(n) != wb || wb < n * 4) {
+      std::printf("FAIL topk_words / topk_grid / topk_work_bytes\n");
+      ++failures;
+    }
+    expect_ok("topk_encode", [&] { topk_encode(w, a, e, pk, work, st, k); });
+    expect_ok("topk_encode no residual", [&] { topk_encode(w, a, none, pk, work, st, k); });
+    expect_ok("topk_encode k 1", [&] { topk_encode(w, a, e, p1, work, st, 1); });
+    expect_ok("topk_encode k n / 2", [&] { topk_encode(w, a, e, ph, work, st, kh); });
+    std::vector<at::Tensor> mk(16);
+    for (int s = 0; s < 16; ++s) mk[s] = T_({wk}, i32);
+    expect_ok("topk_decode_mean M 1", [&] { topk_decode_mean({pk}, a, out, sh, k); });
+    expect_ok("topk_decode_mean M 16", [&] { topk_decode_mean(mk, a, out, sh, k); });
+    expect_ok("topk_decode_mean M 16, no shadow", [&] { topk_decode_mean(mk, a, out, none, k); });
+    expect_ok("topk_decode_mean k 1", [&] { topk_decode_mean({p1}, a, out, sh, 1); });
+    expect_ok("topk_decode_mean k n / 2", [&] { topk_decode_mean({ph, ph}, a, out, none, kh); });
+    // the smallest n: one ragged chunk of 64
+    auto ws = T_({64}, f32), as = T_({64}, f32), es = T_({64}, f32), ps = T_({fd_topk_words(64, 32)}, i32);
+    auto works = T_({fd_topk_work_bytes(64)}, u8), p1s = T_({4}, i32);
+    expect_ok("topk_encode n 64, k n / 2", [&] { topk_encode(ws, as, es, ps, works, st, 32); });
+    expect_ok("topk_encode n 64, k 1, no residual", [&] { topk_encode(ws, as, none, p1s, works, st, 1); });
+    expect_ok("topk_decode_mean n 64", [&] { topk_decode_mean({ps}, as, ws, none, 32); });
+    // extents
+    auto srt = T_({n - 64}, f32), shs = T_({n - 64}, bf), pks = T_({wk - 1}, i32), pkl = T_({wk + 1}, i32);
+    auto work_short = T_({wb - 1}, u8), st7 = T_({7}, f64), st9 = T_({9}, f64);
+    expect_reject("topk_encode short anchor", [&] { topk_encode(w, srt, e, pk, work, st, k); });
+    expect_reject("topk_encode short residual", [&] { topk_encode(w, a, srt, pk, work, st, k); });
+    expect_reject("topk_encode short payload", [&] { topk_encode(w, a, e, pks, work, st, k); });
+    expect_reject("topk_encode long payload", [&] { topk_encode(w, a, e, pkl, work, st, k); });
+    expect_reject("topk_encode payload of another k", [&] { topk_encode(w, a, e, pk, work, st, k + 1); });
+    expect_reject("topk_encode short work", [&] { topk_encode(w, a, e, pk, work_short, st, k); });
+    expect_reject("topk_encode short stats", [&] { topk_encode(w, a, e, pk, work, st7, k); });
+    expect_reject("topk_encode long stats", [&] { topk_encode(w, a, e, pk, work, st9, k); });
+    auto work_odd = T_({wb + 16}, u8).narrow(0, 4, wb);
+    expect_reject("topk_encode misaligned work", [&] { topk_encode(w, a, e, pk, work_odd, st, k); });
+    expect_reject("topk_decode_mean short payload", [&] { topk_decode_mean({mk[0], pks}, a, out, sh, k); });
+    expect_reject("topk_decode_mean payload of another k", [&] { topk_decode_mean({p1}, a, out, sh, k); });
+    expect_reject("topk_decode_mean short anchor", [&] { topk_decode_mean({pk}, srt, out, sh, k); });
+    expect_reject("topk_decode_mean short shadow", [&] { topk_decode_mean({pk}, a, out, shs, k); });
+    // dtypes, layout
+    auto wbf = T_({n}, bf), shf = T_({n}, f32), pkf = T_({wk}, f32), workf = T_({wb / 4 + 4}, f32), stf = T_({8}, f32);
+    expect_reject("topk_encode w dtype", [&] { topk_encode(wbf, a, e, pk, work, st, k); });
+    expect_reject("topk_encode anchor dtype", [&] { topk_encode(w, wbf, e, pk, work, st, k); });
+    expect_reject("topk_encode residual dtype", [&] { topk_encode(w, a, wbf, pk, work, st, k); });
+    expect_reject("topk_encode payload dtype", [&] { topk_encode(w, a, e, pkf, work, st, k); });
+    expect_reject("topk_encode work dtype", [&] { topk_encode(w, a, e, pk, workf, st, k); });
+    expect_reject("topk_encode stats dtype", [&] { topk_encode(w, a, e, pk, work, stf, k); });
+    expect_reject("topk_decode_mean payload dtype", [&] { topk_decode_mean({pkf}, a, out, sh, k); });
+    expect_reject("topk_decode_mean out dtype", [&] { topk_decode_mean({pk}, a, wbf, sh, k); });
+    expect_reject("topk_decode_mean shadow dtype", [&] { topk_decode_mean({pk}, a, out, shf, k); });
+    auto xt = T_({2, n / 2}, f32).t();
+    expect_reject("topk_encode non-contiguous", [&] { topk_encode(xt, a, e, pk, work, st, k); });
+    expect_reject("topk_decode_mean non-contiguous anchor", [&] { topk_decode_mean({pk}, xt, out, sh, k); });
+    // lengths, k, counts
+    auto w60 = T_({2044}, f32), a60 = T_({2044}, f32), w0 = T_({0}, f32), p0 = T_({0}, i32);
+    expect_reject("topk_encode numel % 64", [&] { topk_encode(w60, a60, none, ps, works, st, 32); });
+    expect_reject("topk_encode empty", [&] { topk_encode(w0, w0, none, p0, works, st, 1); });
+    expect_reject("topk_decode_mean numel % 64", [&] { topk_decode_mean({ps}, a60, w60, none, 32); });
+    expect_reject("topk_words numel % 64", [&] { topk_words(100, 1); });
+    expect_reject("topk_words numel 2^31", [&] { topk_words(int64_t(1) << 31, 1); });
+    expect_reject("topk_words k 0", [&] { topk_words(128, 0); });
+    expect_reject("topk_words k above n / 2", [&] { topk_words(128, 65); });
+    expect_reject("topk_work_bytes numel % 64", [&] { topk_work_bytes(100); });
+    expect_reject("topk_encode k 0", [&] { topk_encode(w, a, e, pk, work, st, 0); });
+    expect_reject("topk_encode k < 0", [&] { topk_encode(w, a, e, pk, work, st, -1); });
+    expect_reject("topk_encode k above n / 2", [&] { topk_encode(w, a, e, ph, work, st, kh + 1); });
+    expect_reject("topk_decode_mean k 0", [&] { topk_decode_mean({pk}, a, out, sh, 0); });
+    expect_reject("topk_decode_mean k above n / 2", [&] { topk_decode_mean({ph}, a, out, sh, kh + 1); });
+    expect_reject("topk_decode_mean M 0", [&] { topk_decode_mean({}, a, out, sh, k); });
+    std::vector<at::Tensor> m17(mk);
+    m17.push_back(pk);
+    expect_reject("topk_decode_mean M 17", [&] { topk_decode_mean(m17, a, out, sh, k); });
+    // windows of one allocation
+    auto big = T_({2 * n}, f32);
+    auto lo = big.narrow(0, 0, n), mid = big.narrow(0, n / 2, n), hi = big.narrow(0, n, n);
+    expect_reject("topk_encode anchor is w", [&] { topk_encode(w, w, e, pk, work, st, k); });
+    expect_reject("topk_encode residual is w", [&] { topk_encode(w, a, w, pk, work, st, k); });
+    expect_reject("topk_encode anchor overlaps w", [&] { topk_encode(lo, mid, e, pk, work, st, k); });
+    expect_reject("topk_encode residual overlaps anchor", [&] { topk_encode(w, lo, mid, pk, work, st, k); });
+    expect_ok("topk_encode anchor beside w", [&] { topk_encode(lo, hi, e, pk, work, st, k); });
+    auto pvk = big.narrow(0, n / 2, wk).view(i32);
+    auto workv = big.narrow(0, n / 2, wb / 4).view(u8);
+    expect_reject("topk_encode payload overlaps w", [&] { topk_encode(lo, a, e, pvk, work, st, k); });
+    expect_reject("topk_encode payload overlaps residual", [&] { topk_encode(w, a, lo, pvk, work, st, k); });
+    expect_reject("topk_encode work overlaps w", [&] { topk_encode(lo, a, e, pk, workv, st, k); });
+    expect_reject("topk_encode work overlaps residual", [&] { topk_encode(w, a, hi, pk, workv, st, k); });
+    expect_reject("topk_decode_mean out is anchor", [&] { topk_decode_mean({pk}, a, a, sh, k); });
+    expect_reject("topk_decode_mean out overlaps anchor", [&] { topk_decode_mean({pk}, mid, lo, sh, k); });
+    expect_ok("topk_decode_mean out beside anchor", [&] { topk_decode_mean({pk}, hi, lo, sh, k); });
+    expect_reject("topk_decode_mean out overlaps a payload", [&] { topk_decode_mean({mk[0], pvk}, a, lo, sh, k); });
+    auto shv = big.narrow(0, n / 2, n / 2).view(bf);
+    expect_reject("topk_decode_mean shadow overlaps out", [&] { topk_decode_mean({pk}, a, lo, shv, k); });
+    expect_reject("topk_decode_mean shadow overlaps anchor", [&] { topk_decode_mean({pk}, lo, out, shv, k); });
+    expect_reject("topk_decode_mean shadow overlaps a payload", [&] { topk_decode_mean({pvk}, a, out, shv, k); });
   }
   // ---- embedding backward (work = pieces + LayerNorm partials)
   {

@@ -153,7 +153,8 @@ def _virtual(argv):
                          "rel_l2_local_to_aggregate": c["rel_l2_local_to_aggregate"],
                          "l2_local_to_start": c["l2_local_to_start"],
                          **({k: c[k] for k in ("update_l2", "clipped", "privacy_sigma") if k in c}),
-                         **({k: c[k] for k in ("compress_ratio", "payload_bytes", "quant_error_l2", "bad_groups")
+                         **({k: c[k] for k in ("compress_ratio", "payload_bytes", "quant_error_l2", "bad_groups",
+                                               "bad_elems", "sent", "threshold")
                              if k in c}),  # (--compress: what this client sent)
                          **({"teacher_test": c["teacher_test"]} if "teacher_test" in c else {})}
                         for c in h["clients"]]})

@@ -89,9 +89,12 @@ class FedConfig:
     # Quantized update exchange (parallel/compress.py; QSGD, Alistarh et al. 2017; error feedback,
     # Karimireddy et al. 2019): a client sends w - w_global as int8 / int4 codes with one fp32 scale per 64
     # elements, and keeps what the rounding lost for its next update.  "none": the fp32 exchange (reference)
-    compress: str = "none"                  # "none" | "int8" | "int4"
+    # "topk" (Aji & Heafield 2017; Lin et al. 2018; Stich et al. 2018): only the floor(compress_density * n)
+    # largest-magnitude entries of the update leave, as exact fp32 values with 16-bit chunk-local indices
+    compress: str = "none"                  # "none" | "int8" | "int4" | "topk"
     compress_error_feedback: bool = True    # carry the quantization error into the next round's update
     compress_rounding: str = "nearest"      # "nearest" | "stochastic" (unbiased; Philox keyed by base_seed)
+    compress_density: float = 0.01          # topk: the share of the update's entries sent, in (0, 0.5]
     participation: float = 1.0              # fraction of clients aggregated per round
     timeout_s: float = 300.0                # server.py:10 / client1.py:22
     heartbeat_s: float = 1.0                # failure detection (parallel/health.py); 0 disables

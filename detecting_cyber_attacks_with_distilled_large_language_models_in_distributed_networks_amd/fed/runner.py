@@ -206,7 +206,8 @@ class FederatedClient:
             log.info(f"elastic restart #{restarts}: resuming at round {self.start_round + 1}")
             if self.compress is not None and self.compress.error_feedback:
                 self.compress.reset()
-                log.info("quantization residual lost with the restarted process: error feedback starts again from zero")
+                log.info(("sparsification" if self.compress.bits is None else "quantization")
+                         + " residual lost with the restarted process: error feedback starts again from zero")
         log.info(f"data: {len(self.data.train)} train / {len(self.data.val)} val / {len(self.data.test)} test rows "
                  f"(sampled {self.data.n_rows}), impl={self.model.impl}, device={dev}")
         return self
@@ -524,19 +525,32 @@ def _privacy_fields(rep: Dict, privacy, rounds_done: int) -> Dict:
 
 
 def _compress_line(compress) -> str:
-    """One log line for a job with the quantized exchange."""
-    from ..parallel.compress import payload_ratio
-    return (f"quantized update exchange: int{compress.bits}, {compress.rounding} rounding, error feedback "
+    """One log line for a job with the quantized or sparsified exchange."""
+    from ..parallel.compress import TopKCompressor, payload_ratio
+    if isinstance(compress, TopKCompressor):
+        return (f"sparsified update exchange: {compress.describe()}, error feedback "
+                f"{'on' if compress.error_feedback else 'off'} (about 6 bytes per sent entry)")
+    return (f"quantized update exchange: {compress.describe()}, {compress.rounding} rounding, error feedback "
             f"{'on' if compress.error_feedback else 'off'} (payload {payload_ratio(compress.bits):.2f}x smaller than fp32)")
 
 
 def _compress_fields(rep: Dict) -> Dict:
-    """A record's compression keys from ``Compressor.encode_``'s report."""
-    return {"compress_ratio": rep["ratio"], "payload_bytes": rep["payload_bytes"], "update_l2": rep["update_l2"],
-            "quant_error_l2": rep["error_l2"], "bad_groups": rep["bad_groups"]}
+    """A record's compression keys from ``Compressor.encode_``'s (or ``TopKCompressor.encode_``'s) report."""
+    out = {"compress_ratio": rep["ratio"], "payload_bytes": rep["payload_bytes"], "update_l2": rep["update_l2"],
+           "quant_error_l2": rep["error_l2"]}
+    if "bad_groups" in rep:
+        out["bad_groups"] = rep["bad_groups"]
+    else:  # top-k: the norm held back, the elements left out, the entries sent and the smallest of them
+        out.update(bad_elems=rep["bad_elems"], sent=rep["sent"], threshold=rep["threshold"])
+    return out
 
 
 def _compress_sent_line(comp: Dict) -> str:
+    if "sent" in comp:
+        return (f"sparsified update: {comp['sent']} entries >= {comp['threshold']:.6g} in {comp['payload_bytes']} B "
+                f"({comp['compress_ratio']:.2f}x smaller), |update| = {comp['update_l2']:.6g}, |held back| = "
+                f"{comp['quant_error_l2']:.6g}"
+                + (f", [WARN] {comp['bad_elems']} element(s) with inf / NaN left out" if comp["bad_elems"] else ""))
     return (f"quantized update: {comp['payload_bytes']} B sent ({comp['compress_ratio']:.2f}x smaller), |update| = "
             f"{comp['update_l2']:.6g}, |quantization error| = {comp['quant_error_l2']:.6g}"
             + (f", [WARN] {comp['bad_groups']} group(s) with inf / NaN sent as zero" if comp["bad_groups"] else ""))
@@ -783,10 +797,17 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
             up = math.sqrt(sum(c["update_l2"] ** 2 for c in recs)) if privacy is None else None
             er = math.sqrt(sum(c["quant_error_l2"] ** 2 for c in recs))
             hist[-1].update(compress_ratio=recs[0]["compress_ratio"], payload_bytes=recs[0]["payload_bytes"],
-                            quant_error_l2=er, bad_groups=sum(c["bad_groups"] for c in recs))
-            say(f"round {r + 1}/{rounds} quantized exchange: int{compress.bits}, {recs[0]['payload_bytes']} B per client "
-                f"({recs[0]['compress_ratio']:.2f}x smaller), pooled |quantization error| = {er:.6g}"
-                + (f" of |update| = {up:.6g}" if up is not None else ""))
+                            quant_error_l2=er)
+            if "bad_groups" in recs[0]:
+                hist[-1].update(bad_groups=sum(c["bad_groups"] for c in recs))
+                say(f"round {r + 1}/{rounds} quantized exchange: {compress.describe()}, {recs[0]['payload_bytes']} B per "
+                    f"client ({recs[0]['compress_ratio']:.2f}x smaller), pooled |quantization error| = {er:.6g}"
+                    + (f" of |update| = {up:.6g}" if up is not None else ""))
+            else:
+                hist[-1].update(bad_elems=sum(c["bad_elems"] for c in recs), sent=sum(c["sent"] for c in recs))
+                say(f"round {r + 1}/{rounds} sparsified exchange: {compress.describe()}, {recs[0]['payload_bytes']} B per "
+                    f"client ({recs[0]['compress_ratio']:.2f}x smaller), pooled |held back| = {er:.6g}"
+                    + (f" of |update| = {up:.6g}" if up is not None else ""))
         if privacy is not None:
             hist[-1].update(privacy_epsilon=privacy.epsilon(r + 1))
             say(f"round {r + 1}/{rounds} privacy: epsilon <= {hist[-1]['privacy_epsilon']:.6g} at delta "

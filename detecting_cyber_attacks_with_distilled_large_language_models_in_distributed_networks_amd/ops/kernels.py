@@ -1241,3 +1241,47 @@ def quant_decode_mean(payloads, anchor, out, shadow=None, bits=8):
     (``parallel.compress.torch_decode_mean_`` is the specification).  ``out`` / ``shadow`` overlap no
     input."""
     ext().quant_decode_mean(list(payloads), anchor, out, shadow, int(bits))
+
+
+TOPK_MAX_CLIENTS = 16
+TOPK_CHUNK = 4096  # elements per payload chunk: a local index fits 16 bits
+
+
+def topk_grid(n):
+    """Blocks of the chunk-owning launches of ``topk_encode`` / ``topk_decode_mean`` over ``n`` floats:
+    one per chunk of 4096 elements, at most 1024."""
+    return int(ext().topk_grid(int(n)))
+
+
+def topk_words(n, k):
+    """int32 words of the top-k payload of ``n`` floats (``n % 64 == 0``) with ``k`` entries (``1 <= k <=
+    n / 2``): ``ceil(n / 4096) + 1`` offsets, ``k`` fp32 bit patterns, ``ceil(k / 2)`` words of uint16 local
+    indices."""
+    return int(ext().topk_words(int(n), int(k)))
+
+
+def topk_work_bytes(n):
+    """Bytes of ``topk_encode``'s ``work`` over ``n`` floats: a copy of the update, three histograms, the
+    per-chunk counts and their scans, two doubles per block."""
+    return int(ext().topk_work_bytes(int(n)))
+
+
+def topk_encode(w, anchor, residual, payload, work, stats, k):
+    """``payload`` (int32, ``topk_words(n, k)``) = the ``k`` entries of ``v = (w - anchor) + residual`` with
+    the largest magnitudes, ties by the lower index (sparsify.hip: a three-level radix select over the
+    magnitude bit patterns and an ordered chunked compaction, a fixed sequence of launches with nothing
+    read back; ``parallel.compress.torch_topk_encode_`` is the specification); ``residual`` (optional)
+    becomes what was not sent, in place.  ``stats`` (float64, 8) = [|v|, |e'|, bad elements, sent,
+    threshold, 0, 0, 0]; ``work`` (uint8, >= ``topk_work_bytes(n)``, 16-byte aligned) is scratch.  Two runs
+    give identical bits."""
+    ext().topk_encode(w, anchor, residual, payload, work, stats, int(k))
+
+
+def topk_decode_mean(payloads, anchor, out, shadow=None, k=1):
+    """``out = anchor + mean`` of the M = len(payloads) sparse payloads (1 <= M <= 16, scattered and
+    added in the given order, then times ``float32(1 / M)``), ``shadow`` (optional) = bf16(out), in one
+    dense pass (``parallel.compress.torch_topk_decode_mean_`` is the specification).  No payload content
+    reads or writes out of bounds: offsets are clamped, a local index beyond its chunk is dropped; a
+    payload that repeats an index inside a chunk gets one of the duplicates, which one is unspecified.
+    ``out`` / ``shadow`` overlap no input."""
+    ext().topk_decode_mean(list(payloads), anchor, out, shadow, int(k))

@@ -67,7 +67,7 @@ def fedavg_(model, weight: float = 1.0, participate: bool = True, comm=None, ser
                  aggregate of the participating clients' rows (``_robust_``); unweighted, so ``weight``
                  is not used and the number of participating clients is returned.  Its report is left
                  in ``robust.last``.  None: the code below, untouched.
-    compress:    optional ``parallel.compress.Compressor`` (int8 / int4 codes, error feedback): every
+    compress:    optional ``parallel.compress.Compressor`` (int8 / int4 codes, or top-k entries; error feedback): every
                  participating client encodes ``master - anchor`` (``anchor``: the round's starting
                  weights, a buffer apart from the master; ``client`` / ``round`` select its residual and
                  its stochastic stream), the payloads are all-gathered and their decoded mean is added
@@ -215,7 +215,6 @@ def _compressed_(model, participate: bool, comm, server, compress, anchor, clien
 
     Memory: the gather buffer is ``world x`` the payload -- for DistilBERT (265 MB of fp32 master)
     70.6 MB per client at int8 -- and lives for this call only."""
-    from .compress import payload_words
     A = model.arena
     compress.last = None
     if not _dist_on():
@@ -239,7 +238,7 @@ def _compressed_(model, participate: bool, comm, server, compress, anchor, clien
     if participate:
         mine = compress.encode_(A.master, anchor, client, round)
     else:
-        mine = torch.zeros(payload_words(A.master.numel(), compress.bits), dtype=torch.int32, device=dev)
+        mine = torch.zeros(compress.words(A.master.numel()), dtype=torch.int32, device=dev)
     if use_native:
         rows = comm.all_gather(mine)
     else:
