@@ -175,6 +175,15 @@ int fd_topk_encode(const float* w, const float* anchor, float* residual, int32_t
                    long long k, long long n, hipStream_t st);
 int fd_topk_decode_mean(const int32_t* const* src, int M, const float* anchor, float* out, void* shadow, long long k,
                         long long n, hipStream_t st);
+int fd_secagg_grid(long long n);
+long long fd_secagg_words(long long n);
+int fd_secagg_stream(int32_t* out, const uint32_t* key, uint32_t nonce0, uint32_t nonce1, uint32_t nonce2, int rounds,
+                     long long first_block, long long n, hipStream_t st);
+int fd_secagg_mask(const float* w, const float* anchor, const uint32_t* keys, int P, uint32_t signs, int32_t* payload,
+                   double* partial, double* stats, int frac_bits, int rounds, long long round, long long first_block,
+                   long long n, hipStream_t st);
+int fd_secagg_unmask_mean(const int32_t* const* src, int M, const float* anchor, float* out, void* shadow,
+                          int frac_bits, long long n, hipStream_t st);
 }
 
 namespace {
@@ -2163,6 +2172,144 @@ void topk_decode_mean(const std::vector<at::Tensor>& payloads, const at::Tensor&
            "topk_decode_mean");
 }
 
+// Secure aggregation (secagg.hip).  A payload of n floats is one int32 tensor of n + 16 words: the
+// masked fixed-point codes, then the check block.
+int64_t secagg_grid(int64_t n) { return (int64_t)fd_secagg_grid(n); }
+
+int64_t secagg_words(int64_t n) {
+  TORCH_CHECK(n > 0 && n % 16 == 0 && n <= (std::numeric_limits<int64_t>::max() >> 1) / 8,
+              "secagg_words: numel % 16, got ", n);
+  return (int64_t)fd_secagg_words(n);
+}
+
+void secagg_params_check(int64_t frac_bits, int64_t rounds, const char* what) {
+  TORCH_CHECK(frac_bits >= 8 && frac_bits <= 30, what, ": frac_bits in 8 .. 30, got ", frac_bits);
+  TORCH_CHECK(rounds == 8 || rounds == 12 || rounds == 20, what, ": ChaCha rounds must be 8, 12 or 20, got ", rounds);
+}
+
+// the 32-bit block counters first_block .. first_block + n / 16 - 1 + extra (extra = 1: the check block's)
+void secagg_blocks_check(int64_t first_block, int64_t n, int64_t extra, const char* what) {
+  const int64_t w32 = int64_t(1) << 32;
+  TORCH_CHECK(first_block >= 0 && first_block <= w32 && first_block + n / 16 + extra <= w32, what,
+              ": first_block >= 0 and first_block + numel / 16 + ", extra, " <= 2^32, got ", first_block);
+}
+
+void secagg_aligned(const at::Tensor& t, const char* what, const char* name) {
+  TORCH_CHECK(((uintptr_t)t.data_ptr() & 15u) == 0, what, ": ", name, " must be 16-byte aligned");
+}
+
+// out[i] = the ChaCha word of element 16 * first_block + i for `key` (int32, 8 words, on the device)
+// and the nonce (three 32-bit words): the generator secagg_mask adds, alone.
+void secagg_stream(const at::Tensor& out, const at::Tensor& key, const std::vector<int64_t>& nonce, int64_t rounds,
+                   int64_t first_block) {
+  need(out, at::kInt, "out");
+  need(key, at::kInt, "key");
+  const int64_t n = out.numel();
+  secagg_words(n);
+  TORCH_CHECK(key.numel() == 8, "secagg_stream: key holds 8 words, got ", key.numel());
+  TORCH_CHECK(key.device() == out.device(), "secagg_stream: tensors on one device");
+  TORCH_CHECK(!privacy_overlap(out, key), "secagg_stream: out overlaps key");
+  secagg_aligned(out, "secagg_stream", "out");
+  secagg_params_check(24, rounds, "secagg_stream");
+  const int64_t w32 = int64_t(1) << 32;
+  TORCH_CHECK(nonce.size() == 3, "secagg_stream: the nonce holds 3 words, got ", nonce.size());
+  for (int64_t v : nonce) TORCH_CHECK(v >= 0 && v < w32, "secagg_stream: nonce words in [0, 2^32), got ", v);
+  secagg_blocks_check(first_block, n, 0, "secagg_stream");
+  check_rc(fd_secagg_stream(out.data_ptr<int32_t>(), reinterpret_cast<const uint32_t*>(key.data_ptr<int32_t>()),
+                            (uint32_t)nonce[0], (uint32_t)nonce[1], (uint32_t)nonce[2], (int)rounds, first_block, n,
+                            stream()),
+           "secagg_stream");
+}
+
+// payload (int32, numel + 16) = the fixed-point codes of w - anchor under the signed streams of the P
+// partners (keys: int32 [P, 8]; bit p of signs set: partner p's stream is subtracted; nonce (round, 0,
+// 0)), then the masked check block; stats (float64, 4) = {|d|, |d - float(q) 2^-f|, clamped, bad
+// elements}; partial (float64, >= 4 * grid) receives the per-block sums.  Element i takes the word of
+// global element 16 * first_block + i.  Nothing is launched unless every check passes; no two of w,
+// anchor, keys, payload, partial, stats overlap.
+void secagg_mask(const at::Tensor& w, const at::Tensor& anchor, const at::Tensor& keys, int64_t signs,
+                 const at::Tensor& payload, const at::Tensor& partial, const at::Tensor& stats, int64_t frac_bits,
+                 int64_t rounds, int64_t round, int64_t first_block) {
+  need(w, at::kFloat, "w");
+  need(anchor, at::kFloat, "anchor");
+  need(keys, at::kInt, "keys");
+  need(payload, at::kInt, "payload");
+  need(partial, at::kDouble, "partial");
+  need(stats, at::kDouble, "stats");
+  const int64_t n = w.numel();
+  const int64_t words = secagg_words(n);
+  TORCH_CHECK(anchor.numel() == n, "secagg_mask: anchor has ", anchor.numel(), " elements, w ", n);
+  TORCH_CHECK(payload.numel() == words, "secagg_mask: payload has ", payload.numel(), " words, expected ", words);
+  TORCH_CHECK(keys.dim() == 2 && keys.size(1) == 8, "secagg_mask: keys is [P, 8]");
+  const int64_t P = keys.size(0);
+  TORCH_CHECK(P >= 0 && P <= 15, "secagg_mask: 0 <= P <= 15 partners, got ", P);
+  TORCH_CHECK(signs >= 0 && (signs >> P) == 0, "secagg_mask: signs holds one bit per partner, got ", signs);
+  const auto dev = w.device();
+  TORCH_CHECK(anchor.device() == dev && keys.device() == dev && payload.device() == dev && partial.device() == dev &&
+                  stats.device() == dev,
+              "secagg_mask: tensors on one device");
+  TORCH_CHECK(partial.numel() >= 4 * (int64_t)fd_secagg_grid(n), "secagg_mask: partial size");
+  TORCH_CHECK(stats.numel() == 4, "secagg_mask: stats holds 4 doubles");
+  std::vector<const at::Tensor*> bufs = {&w, &anchor, &payload, &partial, &stats};
+  if (P > 0) bufs.push_back(&keys);
+  for (size_t i = 0; i < bufs.size(); ++i)
+    for (size_t j = i + 1; j < bufs.size(); ++j)
+      TORCH_CHECK(!privacy_overlap(*bufs[i], *bufs[j]), "secagg_mask: buffers ", i, " and ", j, " overlap");
+  secagg_aligned(w, "secagg_mask", "w");
+  secagg_aligned(anchor, "secagg_mask", "anchor");
+  secagg_aligned(payload, "secagg_mask", "payload");
+  secagg_params_check(frac_bits, rounds, "secagg_mask");
+  TORCH_CHECK(round >= 0 && round < (int64_t(1) << 32), "secagg_mask: round in [0, 2^32), got ", round);
+  secagg_blocks_check(first_block, n, 1, "secagg_mask");
+  check_rc(fd_secagg_mask(w.data_ptr<float>(), anchor.data_ptr<float>(),
+                          P > 0 ? reinterpret_cast<const uint32_t*>(keys.data_ptr<int32_t>()) : nullptr, (int)P,
+                          (uint32_t)signs, payload.data_ptr<int32_t>(), partial.data_ptr<double>(),
+                          stats.data_ptr<double>(), (int)frac_bits, (int)rounds, round, first_block, n, stream()),
+           "secagg_mask");
+}
+
+// out = anchor + (float(int32(sum of the M payloads mod 2^32)) * 2^-frac_bits) * float(1 / M) over the
+// first numel words of each payload (1 <= M <= 16), shadow (optional) = bf16(out).  out and shadow
+// overlap no input.
+void secagg_unmask_mean(const std::vector<at::Tensor>& payloads, const at::Tensor& anchor, const at::Tensor& out,
+                        const c10::optional<at::Tensor>& shadow, int64_t frac_bits) {
+  const int64_t M = (int64_t)payloads.size();
+  TORCH_CHECK(M >= 1 && M <= 16, "secagg_unmask_mean: 1 <= M <= 16 payloads, got ", M);
+  need(anchor, at::kFloat, "anchor");
+  need(out, at::kFloat, "out");
+  need_opt(shadow, at::kBFloat16, "shadow");
+  const bool has_shadow = shadow.has_value() && shadow->defined();
+  const int64_t n = out.numel();
+  const int64_t words = secagg_words(n);
+  TORCH_CHECK(anchor.numel() == n, "secagg_unmask_mean: anchor has ", anchor.numel(), " elements, out ", n);
+  if (has_shadow) TORCH_CHECK(shadow->numel() == n, "secagg_unmask_mean: shadow size");
+  const auto dev = out.device();
+  TORCH_CHECK(anchor.device() == dev && (!has_shadow || shadow->device() == dev),
+              "secagg_unmask_mean: tensors on one device");
+  TORCH_CHECK(!privacy_overlap(out, anchor), "secagg_unmask_mean: out overlaps anchor");
+  if (has_shadow)
+    TORCH_CHECK(!privacy_overlap(*shadow, out) && !privacy_overlap(*shadow, anchor),
+                "secagg_unmask_mean: shadow overlaps out or anchor");
+  secagg_aligned(anchor, "secagg_unmask_mean", "anchor");
+  secagg_aligned(out, "secagg_unmask_mean", "out");
+  if (has_shadow) secagg_aligned(*shadow, "secagg_unmask_mean", "shadow");
+  secagg_params_check(frac_bits, 20, "secagg_unmask_mean");
+  const int32_t* ptrs[16];
+  for (int64_t s = 0; s < M; ++s) {
+    need(payloads[s], at::kInt, "payload");
+    TORCH_CHECK(payloads[s].device() == dev, "secagg_unmask_mean: tensors on one device");
+    TORCH_CHECK(payloads[s].numel() == words, "secagg_unmask_mean: payload ", s, " has ", payloads[s].numel(),
+                " words, expected ", words);
+    TORCH_CHECK(!privacy_overlap(payloads[s], out) && (!has_shadow || !privacy_overlap(payloads[s], *shadow)),
+                "secagg_unmask_mean: an output overlaps payload ", s);
+    secagg_aligned(payloads[s], "secagg_unmask_mean", "a payload");
+    ptrs[s] = payloads[s].data_ptr<int32_t>();
+  }
+  check_rc(fd_secagg_unmask_mean(ptrs, (int)M, anchor.data_ptr<float>(), out.data_ptr<float>(), ptr<void>(shadow),
+                                 (int)frac_bits, n, stream()),
+           "secagg_unmask_mean");
+}
+
 }  // namespace
 
 #ifndef FD_HOST_VALIDATION
@@ -2307,5 +2454,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("work"), py::arg("stats"), py::arg("k"));
   m.def("topk_decode_mean", &topk_decode_mean, py::arg("payloads"), py::arg("anchor"), py::arg("out"),
         py::arg("shadow") = py::none(), py::arg("k") = 1);
+  m.def("secagg_grid", &secagg_grid);
+  m.def("secagg_words", &secagg_words);
+  m.def("secagg_stream", &secagg_stream, py::arg("out"), py::arg("key"), py::arg("nonce"), py::arg("rounds") = 20,
+        py::arg("first_block") = 0);
+  m.def("secagg_mask", &secagg_mask, py::arg("w"), py::arg("anchor"), py::arg("keys"), py::arg("signs"),
+        py::arg("payload"), py::arg("partial"), py::arg("stats"), py::arg("frac_bits") = 24, py::arg("rounds") = 20,
+        py::arg("round") = 0, py::arg("first_block") = 0);
+  m.def("secagg_unmask_mean", &secagg_unmask_mean, py::arg("payloads"), py::arg("anchor"), py::arg("out"),
+        py::arg("shadow") = py::none(), py::arg("frac_bits") = 24);
 }
 #endif  // FD_HOST_VALIDATION

@@ -900,6 +900,100 @@ int fd_topk_decode_mean(const int32_t* const* src, int M, const float* anchor, f
   }
   return 0;
 }
+// (csrc/kernels/secagg.hip: one lane per float4, the check block's four behind the tensor, at most 2048 blocks)
+namespace {
+bool hc_secagg_n_ok(long long n) { return n > 0 && n % 16 == 0 && n <= 0x3fffffffffffffffll / 8; }
+bool hc_secagg_blocks_ok(long long first_block, long long n, int extra) {
+  return first_block >= 0 && first_block <= 0x100000000ll && first_block + n / 16 + extra <= 0x100000000ll;
+}
+}  // namespace
+int fd_secagg_grid(long long n) { return n > 0 ? (int)std::min<long long>((n / 4 + 4 + 255) / 256, 2048) : 0; }
+long long fd_secagg_words(long long n) { return hc_secagg_n_ok(n) ? n + 16 : 0; }
+int fd_secagg_stream(int32_t* out, const uint32_t* key, uint32_t, uint32_t, uint32_t, int rounds, long long first_block,
+                     long long n, hipStream_t) {
+  ++hc::calls;
+  // the kernel reads the 8 key words and writes n / 4 uint4 of out
+  if (!hc_secagg_n_ok(n)) {
+    hc::violations.push_back("secagg_stream: n % 16");
+    return 0;
+  }
+  hc::span(out, n * 4, "secagg_stream out");
+  hc::span(key, 32, "secagg_stream key");
+  if (((uintptr_t)out & 15u) != 0) hc::violations.push_back("secagg_stream: out alignment");
+  if (out && key && hc_overlaps(out, n * 4, key, 32)) hc::violations.push_back("secagg_stream: out overlaps key");
+  if (rounds != 8 && rounds != 12 && rounds != 20) hc::violations.push_back("secagg_stream: rounds");
+  if (!hc_secagg_blocks_ok(first_block, n, 0)) hc::violations.push_back("secagg_stream: first_block");
+  return 0;
+}
+int fd_secagg_mask(const float* w, const float* anchor, const uint32_t* keys, int P, uint32_t signs, int32_t* payload,
+                   double* partial, double* stats, int frac_bits, int rounds, long long round, long long first_block,
+                   long long n, hipStream_t) {
+  ++hc::calls;
+  // the kernel reads n / 4 float4 of w and anchor and 8 * P key words, writes n / 4 + 4 uint4 of payload
+  // and four doubles per block of partial; the finalize reads those and writes the four doubles of stats
+  if (!hc_secagg_n_ok(n)) {
+    hc::violations.push_back("secagg_mask: n % 16");
+    return 0;
+  }
+  if (P < 0 || P > 15 || (signs >> P) != 0u) {
+    hc::violations.push_back("secagg_mask: P / signs");
+    return 0;
+  }
+  const long long grid = fd_secagg_grid(n);
+  hc::span(w, n * 4, "secagg_mask w");
+  hc::span(anchor, n * 4, "secagg_mask anchor");
+  if (P > 0) hc::span(keys, 32LL * P, "secagg_mask keys");
+  hc::span(payload, (n + 16) * 4, "secagg_mask payload");
+  hc::span(partial, 4 * 8LL * grid, "secagg_mask partial");
+  hc::span(stats, 32, "secagg_mask stats");
+  if ((((uintptr_t)w | (uintptr_t)anchor | (uintptr_t)payload) & 15u) != 0)
+    hc::violations.push_back("secagg_mask: alignment");
+  const void* bufs[6] = {w, anchor, payload, partial, stats, P > 0 ? keys : nullptr};
+  const long long bytes[6] = {n * 4, n * 4, (n + 16) * 4, 4 * 8LL * grid, 32, 32LL * P};
+  for (int i = 0; i < 6; ++i)
+    for (int j = i + 1; j < 6; ++j)
+      if (bufs[i] && bufs[j] && hc_overlaps(bufs[i], bytes[i], bufs[j], bytes[j]))
+        hc::violations.push_back("secagg_mask: buffers overlap");
+  if (frac_bits < 8 || frac_bits > 30) hc::violations.push_back("secagg_mask: frac_bits");
+  if (rounds != 8 && rounds != 12 && rounds != 20) hc::violations.push_back("secagg_mask: rounds");
+  if (round < 0 || round > 0xffffffffll || !hc_secagg_blocks_ok(first_block, n, 1))
+    hc::violations.push_back("secagg_mask: round / first_block");
+  return 0;
+}
+int fd_secagg_unmask_mean(const int32_t* const* src, int M, const float* anchor, float* out, void* shadow,
+                          int frac_bits, long long n, hipStream_t) {
+  ++hc::calls;
+  // the kernel reads n / 4 uint4 of each of the M payloads (which hold n + 16 words) and as many float4
+  // of anchor, writes as many float4 to out (and uint2 to the shadow)
+  if (!hc_secagg_n_ok(n)) {
+    hc::violations.push_back("secagg_unmask_mean: n % 16");
+    return 0;
+  }
+  if (M < 1 || M > 16 || frac_bits < 8 || frac_bits > 30) {
+    hc::violations.push_back("secagg_unmask_mean: M / frac_bits");
+    return 0;
+  }
+  hc::span(anchor, n * 4, "secagg_unmask_mean anchor");
+  hc::span(out, n * 4, "secagg_unmask_mean out");
+  hc::opt_span(shadow, n * 2, "secagg_unmask_mean shadow");
+  if ((((uintptr_t)anchor | (uintptr_t)out) & 15u) != 0 || ((uintptr_t)shadow & 7u) != 0)
+    hc::violations.push_back("secagg_unmask_mean: alignment");
+  if (anchor && out && hc_overlaps(anchor, n * 4, out, n * 4)) hc::violations.push_back("secagg_unmask_mean: out overlaps anchor");
+  if (shadow && ((out && hc_overlaps(shadow, n * 2, out, n * 4)) || (anchor && hc_overlaps(shadow, n * 2, anchor, n * 4))))
+    hc::violations.push_back("secagg_unmask_mean: shadow overlaps out or anchor");
+  if (!src) {
+    hc::violations.push_back("secagg_unmask_mean: no payloads");
+    return 0;
+  }
+  for (int s = 0; s < M; ++s) {
+    hc::span(src[s], (n + 16) * 4, "secagg_unmask_mean payload");
+    if (((uintptr_t)src[s] & 15u) != 0) hc::violations.push_back("secagg_unmask_mean: payload alignment");
+    if (src[s] && ((out && hc_overlaps(src[s], (n + 16) * 4, out, n * 4)) ||
+                   (shadow && hc_overlaps(src[s], (n + 16) * 4, shadow, n * 2))))
+      hc::violations.push_back("secagg_unmask_mean: an output overlaps a payload");
+  }
+  return 0;
+}
 }  // extern "C"
 
 // ------------------------------------------------------------------ driver
@@ -1808,6 +1902,144 @@ int main() {
     expect_reject("topk_decode_mean shadow overlaps out", [&] { topk_decode_mean({pk}, a, lo, shv, k); });
     expect_reject("topk_decode_mean shadow overlaps anchor", [&] { topk_decode_mean({pk}, lo, out, shv, k); });
     expect_reject("topk_decode_mean shadow overlaps a payload", [&] { topk_decode_mean({pvk}, a, out, shv, k); });
+  }
+  // ---- secure aggregation: w / anchor fp32, the int32 keys [P, 8], the int32 payload of n + 16 words,
+  // four doubles per block
+  {
+    const auto f64 = at::kDouble;
+    const int64_t n = 2048 * 1024 + 16 * 5;  // the grid-stride loop wraps, ragged last sweep
+    const int64_t grid = fd_secagg_grid(n), words = fd_secagg_words(n);
+    auto w = T_({n}, f32), a = T_({n}, f32), sh = T_({n}, bf), out = T_({n}, f32), so = T_({n}, i32);
+    auto k0 = T_({0, 8}, i32), k1 = T_({1, 8}, i32), k15 = T_({15, 8}, i32), key = T_({8}, i32);
+    auto p = T_({words}, i32), part = T_({4 * grid}, f64), st = T_({4}, f64);
+    const int64_t top = (int64_t(1) << 32) - 1;
+    if (secagg_words(n) != n + 16 || secagg_grid(n) != 2048 || secagg_grid(16) != 1) {
+      std::printf("FAIL secagg_words / secagg_grid\n");
+      ++failures;
+    }
+    expect_ok("secagg_stream", [&] { secagg_stream(so, key, {1, 2, 3}, 20, 0); });
+    expect_ok("secagg_stream 8 rounds, top nonce, last blocks", [&] {
+      secagg_stream(so, key, {top, top, top}, 8, (int64_t(1) << 32) - n / 16);
+    });
+    expect_ok("secagg_mask P 0", [&] { secagg_mask(w, a, k0, 0, p, part, st, 24, 20, 0, 0); });
+    expect_ok("secagg_mask P 1", [&] { secagg_mask(w, a, k1, 1, p, part, st, 8, 12, 7, 5); });
+    expect_ok("secagg_mask P 15, top round, last blocks", [&] {
+      secagg_mask(w, a, k15, 0x7fff, p, part, st, 30, 8, top, (int64_t(1) << 32) - n / 16 - 1);
+    });
+    std::vector<at::Tensor> m16(16);
+    for (int s = 0; s < 16; ++s) m16[s] = T_({words}, i32);
+    expect_ok("secagg_unmask_mean M 1", [&] { secagg_unmask_mean({p}, a, out, sh, 24); });
+    expect_ok("secagg_unmask_mean M 16", [&] { secagg_unmask_mean(m16, a, out, sh, 24); });
+    expect_ok("secagg_unmask_mean M 3, no shadow", [&] { secagg_unmask_mean({m16[0], m16[1], p}, a, out, none, 8); });
+    auto rows = T_({3, words}, i32);
+    expect_ok("secagg_unmask_mean rows of a gather", [&] {
+      secagg_unmask_mean({rows.select(0, 0), rows.select(0, 2)}, a, out, sh, 24);
+    });
+    auto ws = T_({16}, f32), as = T_({16}, f32), ps = T_({32}, i32), p4 = T_({4}, f64);
+    expect_ok("secagg_mask small", [&] { secagg_mask(ws, as, k1, 0, ps, p4, st, 24, 20, 0, 0); });
+    expect_ok("secagg_unmask_mean small", [&] { secagg_unmask_mean({ps}, as, ws, none, 24); });
+    // extents
+    auto srt = T_({n - 16}, f32), shs = T_({n - 16}, bf), psh = T_({words - 1}, i32), pl = T_({words + 1}, i32);
+    auto pn = T_({n}, i32), part_short = T_({4 * grid - 1}, f64), st3 = T_({3}, f64), st8 = T_({8}, f64);
+    auto k16 = T_({16, 8}, i32), k7w = T_({1, 7}, i32), kflat = T_({8}, i32), key7 = T_({7}, i32);
+    expect_reject("secagg_mask short anchor", [&] { secagg_mask(w, srt, k1, 0, p, part, st, 24, 20, 0, 0); });
+    expect_reject("secagg_mask short payload", [&] { secagg_mask(w, a, k1, 0, psh, part, st, 24, 20, 0, 0); });
+    expect_reject("secagg_mask long payload", [&] { secagg_mask(w, a, k1, 0, pl, part, st, 24, 20, 0, 0); });
+    expect_reject("secagg_mask payload without the check block", [&] { secagg_mask(w, a, k1, 0, pn, part, st, 24, 20, 0, 0); });
+    expect_reject("secagg_mask short partial", [&] { secagg_mask(w, a, k1, 0, p, part_short, st, 24, 20, 0, 0); });
+    expect_reject("secagg_mask short stats", [&] { secagg_mask(w, a, k1, 0, p, part, st3, 24, 20, 0, 0); });
+    expect_reject("secagg_mask long stats", [&] { secagg_mask(w, a, k1, 0, p, part, st8, 24, 20, 0, 0); });
+    expect_reject("secagg_mask 16 partners", [&] { secagg_mask(w, a, k16, 0, p, part, st, 24, 20, 0, 0); });
+    expect_reject("secagg_mask keys of 7 words", [&] { secagg_mask(w, a, k7w, 0, p, part, st, 24, 20, 0, 0); });
+    expect_reject("secagg_mask flat keys", [&] { secagg_mask(w, a, kflat, 0, p, part, st, 24, 20, 0, 0); });
+    expect_reject("secagg_mask a sign bit beyond P", [&] { secagg_mask(w, a, k1, 2, p, part, st, 24, 20, 0, 0); });
+    expect_reject("secagg_mask signs < 0", [&] { secagg_mask(w, a, k1, -1, p, part, st, 24, 20, 0, 0); });
+    expect_reject("secagg_stream short key", [&] { secagg_stream(so, key7, {1, 2, 3}, 20, 0); });
+    expect_reject("secagg_stream nonce of 2 words", [&] { secagg_stream(so, key, {1, 2}, 20, 0); });
+    expect_reject("secagg_unmask_mean short payload", [&] { secagg_unmask_mean({m16[0], psh}, a, out, sh, 24); });
+    expect_reject("secagg_unmask_mean payload without the check block", [&] { secagg_unmask_mean({pn}, a, out, sh, 24); });
+    expect_reject("secagg_unmask_mean short anchor", [&] { secagg_unmask_mean({p}, srt, out, sh, 24); });
+    expect_reject("secagg_unmask_mean short shadow", [&] { secagg_unmask_mean({p}, a, out, shs, 24); });
+    // dtypes
+    auto wb = T_({n}, bf), pf = T_({words}, f32), partf = T_({4 * grid}, f32), stf = T_({4}, f32), shf = T_({n}, f32);
+    auto k1f = T_({1, 8}, f32), k1l = T_({1, 8}, i64);
+    expect_reject("secagg_mask w dtype", [&] { secagg_mask(wb, a, k1, 0, p, part, st, 24, 20, 0, 0); });
+    expect_reject("secagg_mask anchor dtype", [&] { secagg_mask(w, wb, k1, 0, p, part, st, 24, 20, 0, 0); });
+    expect_reject("secagg_mask keys dtype", [&] { secagg_mask(w, a, k1f, 0, p, part, st, 24, 20, 0, 0); });
+    expect_reject("secagg_mask keys int64", [&] { secagg_mask(w, a, k1l, 0, p, part, st, 24, 20, 0, 0); });
+    expect_reject("secagg_mask payload dtype", [&] { secagg_mask(w, a, k1, 0, pf, part, st, 24, 20, 0, 0); });
+    expect_reject("secagg_mask partial dtype", [&] { secagg_mask(w, a, k1, 0, p, partf, st, 24, 20, 0, 0); });
+    expect_reject("secagg_mask stats dtype", [&] { secagg_mask(w, a, k1, 0, p, part, stf, 24, 20, 0, 0); });
+    expect_reject("secagg_stream out dtype", [&] { secagg_stream(w, key, {1, 2, 3}, 20, 0); });
+    expect_reject("secagg_stream key dtype", [&] { secagg_stream(so, k1f, {1, 2, 3}, 20, 0); });
+    expect_reject("secagg_unmask_mean payload dtype", [&] { secagg_unmask_mean({pf}, a, out, sh, 24); });
+    expect_reject("secagg_unmask_mean out dtype", [&] { secagg_unmask_mean({p}, a, wb, sh, 24); });
+    expect_reject("secagg_unmask_mean shadow dtype", [&] { secagg_unmask_mean({p}, a, out, shf, 24); });
+    // contiguity
+    auto xt = T_({2, n / 2}, f32).t();
+    expect_reject("secagg_mask non-contiguous", [&] { secagg_mask(xt, a, k1, 0, p, part, st, 24, 20, 0, 0); });
+    expect_reject("secagg_unmask_mean non-contiguous anchor", [&] { secagg_unmask_mean({p}, xt, out, sh, 24); });
+    expect_reject("secagg_mask non-contiguous keys", [&] {
+      secagg_mask(w, a, T_({8, 2}, i32).t(), 0, p, part, st, 24, 20, 0, 0);
+    });
+    // values
+    auto w24 = T_({24}, f32), a24 = T_({24}, f32), p40 = T_({40}, i32), w0 = T_({0}, f32), p16 = T_({16}, i32);
+    auto so24 = T_({24}, i32), so0 = T_({0}, i32);
+    expect_reject("secagg_mask numel % 16", [&] { secagg_mask(w24, a24, k1, 0, p40, p4, st, 24, 20, 0, 0); });
+    expect_reject("secagg_mask empty", [&] { secagg_mask(w0, w0, k1, 0, p16, p4, st, 24, 20, 0, 0); });
+    expect_reject("secagg_stream numel % 16", [&] { secagg_stream(so24, key, {1, 2, 3}, 20, 0); });
+    expect_reject("secagg_stream empty", [&] { secagg_stream(so0, key, {1, 2, 3}, 20, 0); });
+    expect_reject("secagg_unmask_mean numel % 16", [&] { secagg_unmask_mean({p40}, a24, w24, none, 24); });
+    expect_reject("secagg_words numel % 16", [&] { secagg_words(100); });
+    expect_reject("secagg_mask frac_bits 7", [&] { secagg_mask(w, a, k1, 0, p, part, st, 7, 20, 0, 0); });
+    expect_reject("secagg_mask frac_bits 31", [&] { secagg_mask(w, a, k1, 0, p, part, st, 31, 20, 0, 0); });
+    expect_reject("secagg_mask 10 rounds", [&] { secagg_mask(w, a, k1, 0, p, part, st, 24, 10, 0, 0); });
+    expect_reject("secagg_mask 0 rounds", [&] { secagg_mask(w, a, k1, 0, p, part, st, 24, 0, 0, 0); });
+    expect_reject("secagg_stream 16 rounds", [&] { secagg_stream(so, key, {1, 2, 3}, 16, 0); });
+    expect_reject("secagg_unmask_mean frac_bits 7", [&] { secagg_unmask_mean({p}, a, out, sh, 7); });
+    expect_reject("secagg_unmask_mean frac_bits 31", [&] { secagg_unmask_mean({p}, a, out, sh, 31); });
+    expect_reject("secagg_unmask_mean M 0", [&] { secagg_unmask_mean({}, a, out, sh, 24); });
+    std::vector<at::Tensor> m17(m16);
+    m17.push_back(p);
+    expect_reject("secagg_unmask_mean M 17", [&] { secagg_unmask_mean(m17, a, out, sh, 24); });
+    expect_reject("secagg_mask round < 0", [&] { secagg_mask(w, a, k1, 0, p, part, st, 24, 20, -1, 0); });
+    expect_reject("secagg_mask round 2^32", [&] { secagg_mask(w, a, k1, 0, p, part, st, 24, 20, top + 1, 0); });
+    expect_reject("secagg_mask first_block < 0", [&] { secagg_mask(w, a, k1, 0, p, part, st, 24, 20, 0, -1); });
+    expect_reject("secagg_mask the check block's counter is 2^32", [&] {
+      secagg_mask(w, a, k1, 0, p, part, st, 24, 20, 0, (int64_t(1) << 32) - n / 16);
+    });
+    expect_reject("secagg_mask first_block overflows", [&] {
+      secagg_mask(w, a, k1, 0, p, part, st, 24, 20, 0, std::numeric_limits<int64_t>::max());
+    });
+    expect_reject("secagg_stream first_block < 0", [&] { secagg_stream(so, key, {1, 2, 3}, 20, -1); });
+    expect_reject("secagg_stream the last counter is 2^32", [&] {
+      secagg_stream(so, key, {1, 2, 3}, 20, (int64_t(1) << 32) - n / 16 + 1);
+    });
+    expect_reject("secagg_stream nonce word < 0", [&] { secagg_stream(so, key, {1, -2, 3}, 20, 0); });
+    expect_reject("secagg_stream nonce word 2^32", [&] { secagg_stream(so, key, {1, 2, top + 1}, 20, 0); });
+    // windows of one allocation
+    auto big = T_({2 * n + 32}, f32);
+    auto lo = big.narrow(0, 0, n), mid = big.narrow(0, n / 2, n), hi = big.narrow(0, n, n);
+    expect_reject("secagg_mask anchor is w", [&] { secagg_mask(w, w, k1, 0, p, part, st, 24, 20, 0, 0); });
+    expect_reject("secagg_mask anchor overlaps w", [&] { secagg_mask(lo, mid, k1, 0, p, part, st, 24, 20, 0, 0); });
+    expect_ok("secagg_mask anchor beside w", [&] { secagg_mask(lo, hi, k1, 0, p, part, st, 24, 20, 0, 0); });
+    auto pv = big.narrow(0, n / 2, words).view(i32);
+    expect_reject("secagg_mask payload overlaps w", [&] { secagg_mask(lo, a, k1, 0, pv, part, st, 24, 20, 0, 0); });
+    expect_reject("secagg_mask payload overlaps anchor", [&] { secagg_mask(w, lo, k1, 0, pv, part, st, 24, 20, 0, 0); });
+    auto kv = big.narrow(0, 8, 8).view(i32).view({1, 8});
+    expect_reject("secagg_mask keys inside w", [&] { secagg_mask(lo, a, kv, 0, p, part, st, 24, 20, 0, 0); });
+    expect_reject("secagg_mask a misaligned w", [&] {
+      secagg_mask(big.narrow(0, 1, n), a, k1, 0, p, part, st, 24, 20, 0, 0);
+    });
+    expect_reject("secagg_stream key inside out", [&] { secagg_stream(pv, pv.narrow(0, 16, 8), {1, 2, 3}, 20, 0); });
+    expect_reject("secagg_unmask_mean out is anchor", [&] { secagg_unmask_mean({p}, a, a, sh, 24); });
+    expect_reject("secagg_unmask_mean out overlaps anchor", [&] { secagg_unmask_mean({p}, mid, lo, sh, 24); });
+    expect_ok("secagg_unmask_mean out beside anchor", [&] { secagg_unmask_mean({p}, hi, lo, sh, 24); });
+    expect_reject("secagg_unmask_mean out overlaps a payload", [&] { secagg_unmask_mean({m16[0], pv}, a, lo, sh, 24); });
+    auto shv = big.narrow(0, n / 2, n / 2).view(bf);
+    expect_reject("secagg_unmask_mean shadow overlaps out", [&] { secagg_unmask_mean({p}, a, lo, shv, 24); });
+    expect_reject("secagg_unmask_mean shadow overlaps anchor", [&] { secagg_unmask_mean({p}, lo, out, shv, 24); });
+    expect_reject("secagg_unmask_mean shadow overlaps a payload", [&] { secagg_unmask_mean({pv}, a, out, shv, 24); });
   }
   // ---- embedding backward (work = pieces + LayerNorm partials)
   {

@@ -156,6 +156,7 @@ def _virtual(argv):
                          **({k: c[k] for k in ("compress_ratio", "payload_bytes", "quant_error_l2", "bad_groups",
                                                "bad_elems", "sent", "threshold")
                              if k in c}),  # (--compress: what this client sent)
+                         **({k: c[k] for k in ("clamped", "masked_with") if k in c}),  # (--secagg)
                          **({"teacher_test": c["teacher_test"]} if "teacher_test" in c else {})}
                         for c in h["clients"]]})
     if cfg.save_checkpoints:

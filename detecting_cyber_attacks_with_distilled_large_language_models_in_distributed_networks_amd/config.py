@@ -17,7 +17,8 @@ from dataclasses import dataclass, field
 from typing import Optional
 
 
-_OPTIONAL_INTS = ("drop_client", "drop_round", "num_clients", "poison_client", "poison_round", "privacy_seed")
+_OPTIONAL_INTS = ("drop_client", "drop_round", "num_clients", "poison_client", "poison_round", "privacy_seed",
+                  "secagg_seed")
 
 
 @dataclass
@@ -95,6 +96,13 @@ class FedConfig:
     compress_error_feedback: bool = True    # carry the quantization error into the next round's update
     compress_rounding: str = "nearest"      # "nearest" | "stochastic" (unbiased; Philox keyed by base_seed)
     compress_density: float = 0.01          # topk: the share of the update's entries sent, in (0, 0.5]
+    # Secure aggregation (parallel/secagg.py; Bonawitz et al., CCS 2017): a client sends w - w_global as
+    # 32-bit fixed point under one ChaCha stream per live partner (pair keys by X25519), added with
+    # opposite signs by the two ends of a pair: the streams cancel in the sum and nowhere else
+    secagg: bool = False                    # False: the fp32 exchange (reference)
+    secagg_frac_bits: int = 24              # fraction bits of the fixed point, 8 .. 30
+    secagg_chacha_rounds: int = 20          # 8 | 12 | 20
+    secagg_seed: Optional[int] = None       # None: private keys from os.urandom; an int: derived (tests)
     participation: float = 1.0              # fraction of clients aggregated per round
     timeout_s: float = 300.0                # server.py:10 / client1.py:22
     heartbeat_s: float = 1.0                # failure detection (parallel/health.py); 0 disables

@@ -33,6 +33,7 @@ from ..parallel.dp import DPShardLoader, GradSync, dp_seed_offset, make_topology
 from ..parallel.compress import check_compress_config, make_compressor
 from ..parallel.fedavg import broadcast_model, fedavg_
 from ..parallel.privacy import check_privacy_config, make_privatizer
+from ..parallel.secagg import check_secagg_config, make_secagg
 from ..parallel.robust import check_robust_config, make_robust, most_trimmed, robust_aggregate_
 from ..parallel.server_opt import check_server_config, make_server_optimizer
 from ..utils import checkpoint as ck
@@ -114,6 +115,7 @@ class FederatedClient:
         check_robust_config(cfg)  # (likewise: an unknown aggregator, tcp, weighted_fedavg)
         check_privacy_config(cfg, self.topo.gpus_per_client)  # (a bad clip / noise / delta, weighted_fedavg, replicas)
         check_compress_config(cfg, self.topo.gpus_per_client)  # (an unknown width, tcp, a robust aggregator, ...)
+        check_secagg_config(cfg, self.topo.gpus_per_client, self.num_clients)  # (tcp, a robust aggregator, compress, ...)
         log.phase("Starting client")
         with self.timer("preprocess"):
             if self.frame is None:
@@ -197,7 +199,16 @@ class FederatedClient:
         self.compress = make_compressor(cfg, self.topo.gpus_per_client)
         if self.compress is not None:
             log.info(_compress_line(self.compress))
-        self._round_anchor = None  # the round's starting weights: what privacy and compression measure against
+        # Secure aggregation (parallel/secagg.py; None: secagg off, today's path): a fresh key pair per
+        # process -- so also after an elastic restart -- and one all-gather of the public keys
+        self.secagg = make_secagg(cfg, self.topo.gpus_per_client, self.num_clients, log=log.info)
+        if self.secagg is not None:
+            if self.di.distributed:
+                self.secagg.setup_keys(self.idx, self.num_clients, comm=self.comm, device=dev)
+            else:  # (one process: its own client, or every virtual client -- which hides nothing)
+                self.secagg.setup_keys(range(self.num_clients), self.num_clients)
+            log.info(_secagg_line(self.secagg, self.num_clients))
+        self._round_anchor = None  # the round's starting weights: what privacy, compression and secagg measure against
         self.health = None
         if self.di.distributed and cfg.heartbeat_s > 0 and cfg.transport != "tcp":
             self.health = health.start(cfg.heartbeat_s, cfg.heartbeat_stale_s, cfg.timeout_s)
@@ -296,8 +307,8 @@ class FederatedClient:
         log.phase(f"Starting round {r + 1}/{cfg.rounds}")
         opt = make_optimizer(model, cfg, r, cfg.rounds, cfg.epochs * len(self.train_loader))
         opt.reset_state()  # a fresh Adam every round (client1.py:380), "has state" row flags included
-        if self.privacy is not None or self.compress is not None:
-            # the round's starting weights: what the update is measured (clipped, quantized) against
+        if self.privacy is not None or self.compress is not None or self.secagg is not None:
+            # the round's starting weights: what the update is measured (clipped, quantized, masked) against
             if self._round_anchor is None:
                 self._round_anchor = torch.empty_like(model.arena.master)
             with torch.no_grad():
@@ -386,6 +397,10 @@ class FederatedClient:
                 # privatize, then poison, then encode: quantizing a privatized update is post-processing
                 total_w = fedavg_(model, participate=contributes, comm=self.comm, server=self.server,
                                   compress=self.compress, anchor=self._round_anchor, client=self.idx, round=r)
+            elif self.secagg is not None:
+                # privatize, then poison, then mask: what leaves is the fixed-point update under the pair streams
+                total_w = fedavg_(model, participate=contributes, comm=self.comm, server=self.server,
+                                  secagg=self.secagg, anchor=self._round_anchor, client=self.idx, round=r)
             else:
                 total_w = fedavg_(model, weight=weight, participate=contributes, comm=self.comm, server=self.server)
             if model.device.type == "cuda":
@@ -403,6 +418,9 @@ class FederatedClient:
         comp = _compress_fields(self.compress.last) if self.compress is not None and self.compress.last else None
         if comp is not None:
             log.info(_compress_sent_line(comp))
+        sec = _secagg_fields(self.secagg.last) if self.secagg is not None and self.secagg.last else None
+        if sec is not None:
+            log.info(_secagg_sent_line(sec))
         if self.di.is_main and cfg.save_checkpoints:
             # weights, the server optimizer's moments, then the round tag (_resume)
             ck.save_global(model, cfg.out_dir, r + 1, server=self.server)
@@ -433,6 +451,8 @@ class FederatedClient:
             rec.update(trimmed_share=trim["trimmed_share"], k=trim["k"])
         if comp is not None:  # (after the trim keys, before privacy's: update_l2 is privacy's when both are on)
             rec.update(comp)
+        if sec is not None:  # (likewise: update_l2 is privacy's when both are on)
+            rec.update(sec)
         if priv is not None:
             rec.update(priv)
         elif self.privacy is not None:  # (not sampled this round: nothing of this client was released)
@@ -556,6 +576,25 @@ def _compress_sent_line(comp: Dict) -> str:
             + (f", [WARN] {comp['bad_groups']} group(s) with inf / NaN sent as zero" if comp["bad_groups"] else ""))
 
 
+def _secagg_line(secagg, n_clients: int) -> str:
+    """One log line for a job with secure aggregation."""
+    return (f"secure aggregation: {secagg.describe()}, pairwise X25519 keys among {n_clients} client(s); "
+            f"honest-but-curious participants, no dropout recovery (parallel/secagg.py states the limits)")
+
+
+def _secagg_fields(rep: Dict) -> Dict:
+    """A record's secure-aggregation keys from ``SecureAggregator.mask_``'s report."""
+    return {"payload_bytes": rep["payload_bytes"], "update_l2": rep["update_l2"], "quant_error_l2": rep["error_l2"],
+            "clamped": rep["clamped"], "bad_elems": rep["bad_elems"], "masked_with": rep["masked_with"]}
+
+
+def _secagg_sent_line(sec: Dict) -> str:
+    return (f"masked update: {sec['payload_bytes']} B sent under {sec['masked_with']} pair stream(s), |update| = "
+            f"{sec['update_l2']:.6g}, |fixed-point error| = {sec['quant_error_l2']:.6g}"
+            + (f", [WARN] {sec['clamped']} element(s) clamped at +-2^27 steps" if sec["clamped"] else "")
+            + (f", [WARN] {sec['bad_elems']} element(s) with inf / NaN sent as zero" if sec["bad_elems"] else ""))
+
+
 def _trim_line(trim: Dict) -> str:
     """One log line for a robust round: the most-trimmed slot (the j-th participating client, in
     client order) and its share; honest i.i.d. clients sit near 2k / M each."""
@@ -663,6 +702,13 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
     ``compress_ratio`` / ``payload_bytes`` / ``update_l2`` / ``quant_error_l2`` / ``bad_groups``
     (tests/test_compress_cpu.py: equal to the 2-rank gloo run bit for bit).
 
+    With secure aggregation (``cfg.secagg``, parallel/secagg.py) every client's copy -- after privacy and
+    poisoning -- is masked against the round's start with its own key pair (the job's ``client.secagg`` holds
+    one per virtual client: the arithmetic is exercised, nothing is hidden), and ``unmask_mean_`` of the
+    payloads takes the place of ``_average_masters``: the calls ``fedavg_(..., secagg=)`` makes.  Each client
+    record carries ``payload_bytes`` / ``update_l2`` / ``quant_error_l2`` / ``clamped`` / ``bad_elems`` /
+    ``masked_with`` (tests/test_secagg_cpu.py: equal to the 2-rank gloo run bit for bit).
+
     Returns ``rounds`` (one record per round: per-client local / aggregated metrics, the pooled
     aggregated confusion, the FedAvg time) plus the LAST round's ``clients`` /
     ``aggregated_confusion`` / ``fedavg_ms`` at the top level (the 1-round API of earlier rounds).
@@ -693,6 +739,13 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
     compress = getattr(client, "compress", None)
     if compress is not None and robust is not None:
         raise ValueError("compress needs aggregator='mean'")
+    # the job's SecureAggregator (None: secagg off) -- one key pair per virtual client, all in this process
+    secagg = getattr(client, "secagg", None)
+    if secagg is not None:
+        if robust is not None or compress is not None:
+            raise ValueError("secagg needs aggregator='mean' and compress='none'")
+        if sorted(secagg.private) != list(range(n_clients)):
+            secagg.setup_keys(range(n_clients), n_clients)
     t_init = teacher.arena.master.detach().clone() if teacher is not None else None
     say = progress or (lambda msg: None)
     # per-client state that survives the rounds (a real client's process keeps it)
@@ -754,6 +807,10 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
                 payloads.append(compress.encode_(locals_[-1], glob, v, r))
                 for key, val in _compress_fields(compress.last).items():
                     rec.setdefault(key, val)  # (update_l2 stays privacy's when both are on)
+            if secagg is not None:  # (what leaves the client: its fixed-point update under the pair streams)
+                payloads.append(secagg.mask_(locals_[-1], glob, v, r, range(n_clients)))
+                for key, val in _secagg_fields(secagg.last).items():
+                    rec.setdefault(key, val)
             rec.update({"train": tr, "train_wall_s": time.perf_counter() - t0, "local_test": local})
             # client drift: how far the local epochs moved this client from the round's start
             rec["l2_local_to_start"] = float((locals_[-1] - glob).norm())
@@ -768,6 +825,10 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
             norms = server.last if server is not None else None
         elif compress is not None:
             compress.decode_mean_(model, payloads, glob, server)
+            norms = server.last if server is not None else None
+            del payloads
+        elif secagg is not None:
+            secagg.unmask_mean_(model, payloads, glob, server, round=r)
             norms = server.last if server is not None else None
             del payloads
         elif server is None:
@@ -808,6 +869,13 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
                 say(f"round {r + 1}/{rounds} sparsified exchange: {compress.describe()}, {recs[0]['payload_bytes']} B per "
                     f"client ({recs[0]['compress_ratio']:.2f}x smaller), pooled |held back| = {er:.6g}"
                     + (f" of |update| = {up:.6g}" if up is not None else ""))
+        if secagg is not None:
+            er = math.sqrt(sum(c["quant_error_l2"] ** 2 for c in recs))
+            hist[-1].update(payload_bytes=recs[0]["payload_bytes"], quant_error_l2=er,
+                            clamped=sum(c["clamped"] for c in recs), bad_elems=sum(c["bad_elems"] for c in recs),
+                            masked_with=recs[0]["masked_with"])
+            say(f"round {r + 1}/{rounds} secure aggregation: {secagg.describe()}, {recs[0]['payload_bytes']} B per "
+                f"client under {recs[0]['masked_with']} pair stream(s), pooled |fixed-point error| = {er:.6g}")
         if privacy is not None:
             hist[-1].update(privacy_epsilon=privacy.epsilon(r + 1))
             say(f"round {r + 1}/{rounds} privacy: epsilon <= {hist[-1]['privacy_epsilon']:.6g} at delta "

@@ -1285,3 +1285,45 @@ def topk_decode_mean(payloads, anchor, out, shadow=None, k=1):
     payload that repeats an index inside a chunk gets one of the duplicates, which one is unspecified.
     ``out`` / ``shadow`` overlap no input."""
     ext().topk_decode_mean(list(payloads), anchor, out, shadow, int(k))
+
+
+SECAGG_MAX_CLIENTS = 16
+
+
+def secagg_grid(n):
+    """Blocks of a ``secagg_mask`` launch over ``n`` floats (its ``partial`` holds four doubles per
+    block): one lane per float4 plus the check block's four, at most 2048 blocks of 256 lanes."""
+    return int(ext().secagg_grid(int(n)))
+
+
+def secagg_words(n):
+    """int32 words of the secure-aggregation payload of ``n`` floats (``n % 16 == 0``): one masked
+    fixed-point code per element, then the 16 words of the check block."""
+    return int(ext().secagg_words(int(n)))
+
+
+def secagg_stream(out, key, nonce, rounds=20, first_block=0):
+    """``out[i]`` (int32) = the ChaCha word of element ``16 * first_block + i`` for ``key`` (int32, 8
+    words, on the device) and ``nonce`` (three 32-bit words): the generator ``secagg_mask`` adds, alone
+    (secagg.hip; ``parallel.secagg.stream_words`` is its host mirror, bit for bit)."""
+    ext().secagg_stream(out, key, [int(v) for v in nonce], int(rounds), int(first_block))
+
+
+def secagg_mask(w, anchor, keys, signs, payload, partial, stats, frac_bits=24, rounds=20, round=0, first_block=0):
+    """``payload`` (int32, ``secagg_words(n)``) = the fixed-point codes of ``w - anchor`` under the P =
+    ``keys.shape[0]`` partners' ChaCha streams (``keys`` int32 [P, 8], 0 <= P <= 15; bit p of ``signs``
+    set: stream p is subtracted; nonce ``(round, 0, 0)``), then the masked check block, in one pass plus
+    a one-block finalize (``parallel.secagg.torch_encode`` / ``torch_mask`` are the specification).
+    ``stats`` (float64, 4) = [|d|, |d - float(q) 2^-f|, clamped, bad elements]; ``partial`` (float64, >= 4
+    * ``secagg_grid(n)``, every entry written).  Element i takes the word of global element ``16 *
+    first_block + i``.  P = 0 is the plain quantizer."""
+    ext().secagg_mask(w, anchor, keys, int(signs), payload, partial, stats, int(frac_bits), int(rounds), int(round),
+                      int(first_block))
+
+
+def secagg_unmask_mean(payloads, anchor, out, shadow=None, frac_bits=24):
+    """``out = anchor + (float(int32(sum of the M payloads mod 2^32)) * 2^-frac_bits) * float32(1 / M)``
+    over the payloads' first n words (1 <= M <= 16), ``shadow`` (optional) = bf16(out), in one dense pass
+    (``parallel.secagg.torch_unmask_mean_`` is the specification).  ``out`` / ``shadow`` overlap no
+    input."""
+    ext().secagg_unmask_mean(list(payloads), anchor, out, shadow, int(frac_bits))

@@ -15,7 +15,9 @@ average of the live clients), and FedOpt server optimizers (``fedavg_(..., serve
 parallel/server_opt.py: the same all-reduce, then one fused server step on the sum instead of the
 scale), and Byzantine-robust aggregation (``fedavg_(..., robust=)``, parallel/robust.py: an
 all-gather instead of the sum, then one fused pass that takes the coordinate-wise trimmed mean or
-median of the participating clients).
+median of the participating clients), and secure aggregation (``fedavg_(..., secagg=)``,
+parallel/secagg.py: the clients' fixed-point updates are all-gathered under pairwise ChaCha masks that
+cancel in their modular sum, and one fused pass unmasks the mean).
 
 ``aggregate_state_dicts`` keeps the reference's server-side API for
 state_dict lists (floating tensors only -- an int64 buffer would make the
@@ -51,7 +53,7 @@ def broadcast_model(model, src: int = 0, comm=None):
 
 @torch.no_grad()
 def fedavg_(model, weight: float = 1.0, participate: bool = True, comm=None, server=None, robust=None,
-            compress=None, anchor=None, client: int = 0, round: int = 0) -> float:
+            compress=None, anchor=None, client: int = 0, round: int = 0, secagg=None) -> float:
     """In-place FedAvg of ``model`` across all ranks; returns the total weight.
 
     weight:      this client's aggregation weight (1 = unweighted, n_k = sample-weighted)
@@ -74,7 +76,21 @@ def fedavg_(model, weight: float = 1.0, participate: bool = True, comm=None, ser
                  to the anchor (``_compressed_``); unweighted, so ``weight`` is not used and the number
                  of participating clients is returned.  Its report is left in ``compress.last``.  None:
                  the code below, untouched.
+    secagg:      optional ``parallel.secagg.SecureAggregator``: every participating client sends the
+                 fixed-point codes of ``master - anchor`` under the ChaCha streams it shares with the
+                 round's other live clients (``client`` is its index, ``round`` goes into the nonce), the
+                 payloads are all-gathered, and the mean of their modular sum -- in which the streams
+                 cancel -- is added to the anchor (``_secagg_``); unweighted, so ``weight`` is not used and
+                 the number of participating clients is returned.  Its report is left in ``secagg.last``.
+                 None: the code below, untouched.
     """
+    if secagg is not None:
+        if robust is not None or compress is not None:
+            raise ValueError("secure aggregation takes the plain mean of uncompressed updates (robust=None, "
+                             "compress=None)")
+        if anchor is None:
+            raise ValueError("secure aggregation needs the round's starting weights (anchor=)")
+        return _secagg_(model, participate, comm, server, secagg, anchor, client, round)
     if compress is not None:
         if robust is not None:
             raise ValueError("the quantized exchange takes the plain mean (robust=None)")
@@ -248,6 +264,56 @@ def _compressed_(model, participate: bool, comm, server, compress, anchor, clien
         else:
             dist.all_gather(list(rows.unbind(0)), mine)
     compress.decode_mean_(model, [rows[c] for c in live], anchor, server)
+    del rows
+    return float(len(live))
+
+
+@torch.no_grad()
+def _secagg_(model, participate: bool, comm, server, secagg, anchor, client: int, round: int) -> float:
+    """``fedavg_`` with secure aggregation (parallel/secagg.py): every rank learns the live set from an
+    all-reduced flag vector (one slot per rank = client) *before* anything is encoded, a participating
+    rank masks the fixed-point codes of ``master - anchor`` with the streams of the live partners only --
+    a rank that does not participate sends a row of zeros that no rank reads -- the int32 payloads are
+    all-gathered, the summed check block is compared, and ``unmask_mean_`` adds the mean of the live
+    rows' modular sum to the anchor in one fused pass on the GPU; with a server optimizer its step
+    follows.  Every rank unmasks the same rows, so the ranks stay identical.
+
+    Memory: the gather buffer is ``world x`` the payload (4 bytes per element, as the fp32 master) and
+    lives for this call only."""
+    A = model.arena
+    secagg.last = None
+    if not _dist_on():
+        if not participate:
+            return 0.0
+        secagg.unmask_mean_(model, [secagg.mask_(A.master, anchor, client, round, [client])], anchor, server,
+                            round=round)
+        return 1.0
+    world, rank = dist.get_world_size(), dist.get_rank()
+    dev = A.master.device
+    use_native = comm is not None and A.master.is_cuda
+    flags = torch.zeros(world, dtype=torch.float64, device=dev)
+    flags[rank] = 1.0 if participate else 0.0
+    if use_native:
+        comm.all_reduce_(flags, "sum")
+    else:
+        dist.all_reduce(flags, op=dist.ReduceOp.SUM)
+    flags = flags.tolist()
+    live = [c for c in range(world) if flags[c] > 0.0]
+    if not live:
+        raise RuntimeError("FedAvg round with no participating clients")
+    if participate:
+        mine = secagg.mask_(A.master, anchor, client, round, live)
+    else:
+        mine = torch.zeros(secagg.words(A.master.numel()), dtype=torch.int32, device=dev)
+    if use_native:
+        rows = comm.all_gather(mine)
+    else:
+        rows = torch.empty((world, mine.numel()), dtype=torch.int32, device=dev)
+        if mine.is_cuda:
+            dist.all_gather_into_tensor(rows, mine)
+        else:
+            dist.all_gather(list(rows.unbind(0)), mine)
+    secagg.unmask_mean_(model, [rows[c] for c in live], anchor, server, round=round)
     del rows
     return float(len(live))
 
