@@ -153,6 +153,14 @@ int fd_server_opt(float* master, float* x, float* m, float* v, void* shadow, lon
 int fd_robust_agg_grid(long long n);
 int fd_robust_agg(const float* const* src, int M, int k, float* out, void* shadow, int* counts, long long n,
                   hipStream_t st);
+int fd_robust_dist_grid(long long n);
+int fd_robust_pairdist(const float* const* src, int M, double* partial, long long n, hipStream_t st);
+int fd_robust_krum_finalize(const double* partial, int grid, int M, int f, int m, float* ctl, double* stats,
+                            hipStream_t st);
+int fd_robust_wmean(const float* const* src, int M, const float* ctl, float* out, void* shadow, double* partial,
+                    long long n, hipStream_t st);
+int fd_robust_geomed_finalize(const double* partial, int grid, int M, double nu, int iter, float* ctl, double* stats,
+                              hipStream_t st);
 int fd_privacy_grid(long long n);
 int fd_privacy_norm(const float* w, const float* anchor, double* partial, float* stats, float clip, long long n,
                     hipStream_t st);
@@ -1904,6 +1912,116 @@ void robust_agg(const std::vector<at::Tensor>& srcs, int64_t k, const at::Tensor
 // Blocks of a robust_agg launch over n floats (the counts buffer holds 17 ints per block).
 int64_t robust_agg_grid(int64_t n) { return (int64_t)fd_robust_agg_grid(n); }
 
+// Distance-based robust aggregation (robust_dist.hip; the specification is parallel/robust_dist.py).
+// The sources of a pairdist / wmean call: 2 .. 16 contiguous fp32 tensors of one length n, n % 4 == 0,
+// on one device; their pointers are left in ptrs.
+int64_t robust_dist_sources(const std::vector<at::Tensor>& srcs, const float** ptrs, const char* what) {
+  const int64_t M = (int64_t)srcs.size();
+  TORCH_CHECK(M >= 2 && M <= 16, what, ": 2 <= M <= 16 sources, got ", M);
+  need(srcs[0], at::kFloat, "source");
+  const int64_t n = srcs[0].numel();
+  TORCH_CHECK(n > 0 && n % 4 == 0, what, ": numel % 4");
+  for (int64_t s = 0; s < M; ++s) {
+    need(srcs[s], at::kFloat, "source");
+    TORCH_CHECK(srcs[s].device() == srcs[0].device(), what, ": tensors on one device");
+    TORCH_CHECK(srcs[s].numel() == n, what, ": source ", s, " has ", srcs[s].numel(), " elements, source 0 ", n);
+    ptrs[s] = srcs[s].data_ptr<float>();
+  }
+  return n;
+}
+
+// partial (fp64, >= grid * M (M - 1) / 2) = per block the sums of (src_i - src_j)^2, i < j.
+void robust_pairdist(const std::vector<at::Tensor>& srcs, const at::Tensor& partial) {
+  const float* ptrs[16];
+  const int64_t n = robust_dist_sources(srcs, ptrs, "robust_pairdist");
+  const int64_t M = (int64_t)srcs.size();
+  need(partial, at::kDouble, "partial");
+  TORCH_CHECK(partial.device() == srcs[0].device(), "robust_pairdist: tensors on one device");
+  TORCH_CHECK(partial.numel() >= M * (M - 1) / 2 * (int64_t)fd_robust_dist_grid(n), "robust_pairdist: partial size");
+  check_rc(fd_robust_pairdist(ptrs, (int)M, partial.data_ptr<double>(), n, stream()), "robust_pairdist");
+}
+
+// ctl (fp32, >= 20) / stats (fp64, >= 288) = krum_select of the grid x M (M - 1) / 2 partials.
+void robust_krum_finalize(const at::Tensor& partial, int64_t grid, int64_t M, int64_t f, int64_t m,
+                          const at::Tensor& ctl, const at::Tensor& stats) {
+  TORCH_CHECK(M >= 2 && M <= 16, "robust_krum_finalize: 2 <= M <= 16, got ", M);
+  TORCH_CHECK(grid >= 1 && grid <= 4096, "robust_krum_finalize: 1 <= grid <= 4096, got ", grid);
+  TORCH_CHECK(f >= 0, "robust_krum_finalize: f >= 0, got ", f);
+  TORCH_CHECK(m >= 1 && m <= M, "robust_krum_finalize: 1 <= m <= M, got m = ", m, " with M = ", M);
+  need(partial, at::kDouble, "partial");
+  need(ctl, at::kFloat, "ctl");
+  need(stats, at::kDouble, "stats");
+  TORCH_CHECK(ctl.device() == partial.device() && stats.device() == partial.device(),
+              "robust_krum_finalize: tensors on one device");
+  TORCH_CHECK(partial.numel() >= grid * (M * (M - 1) / 2), "robust_krum_finalize: partial size");
+  TORCH_CHECK(ctl.numel() >= 20, "robust_krum_finalize: ctl size");
+  TORCH_CHECK(stats.numel() >= 288, "robust_krum_finalize: stats size");
+  check_rc(fd_robust_krum_finalize(partial.data_ptr<double>(), (int)grid, (int)M, (int)std::min<int64_t>(f, 1 << 20),
+                                   (int)m, ctl.data_ptr<float>(), stats.data_ptr<double>(), stream()),
+           "robust_krum_finalize");
+}
+
+// out (optional) = the ctl-weighted sum of the sources, shadow (optional, with out) = bf16(out), partial
+// (optional, fp64, >= (M + 1) * grid) = per block the squared distances to out and the non-finite outputs.
+void robust_wmean(const std::vector<at::Tensor>& srcs, const at::Tensor& ctl, const c10::optional<at::Tensor>& out,
+                  const c10::optional<at::Tensor>& shadow, const c10::optional<at::Tensor>& partial) {
+  const float* ptrs[16];
+  const int64_t n = robust_dist_sources(srcs, ptrs, "robust_wmean");
+  const int64_t M = (int64_t)srcs.size();
+  need(ctl, at::kFloat, "ctl");
+  need_opt(out, at::kFloat, "out");
+  need_opt(shadow, at::kBFloat16, "shadow");
+  need_opt(partial, at::kDouble, "partial");
+  const bool has_out = out.has_value() && out->defined();
+  const bool has_shadow = shadow.has_value() && shadow->defined();
+  const bool has_partial = partial.has_value() && partial->defined();
+  const auto dev = srcs[0].device();
+  TORCH_CHECK(ctl.device() == dev && (!has_out || out->device() == dev) && (!has_shadow || shadow->device() == dev) &&
+                  (!has_partial || partial->device() == dev),
+              "robust_wmean: tensors on one device");
+  TORCH_CHECK(ctl.numel() >= 20, "robust_wmean: ctl size");
+  TORCH_CHECK(has_out || !has_shadow, "robust_wmean: shadow without out");
+  if (has_out) TORCH_CHECK(out->numel() == n, "robust_wmean: out size");
+  if (has_shadow) TORCH_CHECK(shadow->numel() == n, "robust_wmean: shadow size");
+  if (has_partial)
+    TORCH_CHECK(partial->numel() >= (M + 1) * (int64_t)fd_robust_dist_grid(n), "robust_wmean: partial size");
+  const auto overlaps = [](const void* a, int64_t abytes, const void* b, int64_t bbytes) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + (uintptr_t)bbytes && b0 < a0 + (uintptr_t)abytes;
+  };
+  for (int64_t s = 0; s < M; ++s) {
+    if (has_out) TORCH_CHECK(!overlaps(ptrs[s], n * 4, out->data_ptr(), n * 4), "robust_wmean: out overlaps source ", s);
+    if (has_shadow)
+      TORCH_CHECK(!overlaps(ptrs[s], n * 4, shadow->data_ptr(), n * 2), "robust_wmean: shadow overlaps source ", s);
+  }
+  check_rc(fd_robust_wmean(ptrs, (int)M, ctl.data_ptr<float>(), ptr<float>(out), ptr<void>(shadow), ptr<double>(partial),
+                           n, stream()),
+           "robust_wmean");
+}
+
+// ctl (fp32, >= 20) / row iter of stats (fp64, rows of 34) = geomed_weights of the grid x (M + 1) partials.
+void robust_geomed_finalize(const at::Tensor& partial, int64_t grid, int64_t M, double nu, int64_t iter,
+                            const at::Tensor& ctl, const at::Tensor& stats) {
+  TORCH_CHECK(M >= 2 && M <= 16, "robust_geomed_finalize: 2 <= M <= 16, got ", M);
+  TORCH_CHECK(grid >= 1 && grid <= 4096, "robust_geomed_finalize: 1 <= grid <= 4096, got ", grid);
+  TORCH_CHECK(std::isfinite(nu) && nu > 0.0, "robust_geomed_finalize: nu > 0 and finite");
+  need(partial, at::kDouble, "partial");
+  need(ctl, at::kFloat, "ctl");
+  need(stats, at::kDouble, "stats");
+  TORCH_CHECK(ctl.device() == partial.device() && stats.device() == partial.device(),
+              "robust_geomed_finalize: tensors on one device");
+  TORCH_CHECK(partial.numel() >= grid * (M + 1), "robust_geomed_finalize: partial size");
+  TORCH_CHECK(ctl.numel() >= 20, "robust_geomed_finalize: ctl size");
+  TORCH_CHECK(iter >= 0 && iter < stats.numel() / 34, "robust_geomed_finalize: iter ", iter, " outside the ",
+              stats.numel() / 34, " stats rows");
+  check_rc(fd_robust_geomed_finalize(partial.data_ptr<double>(), (int)grid, (int)M, nu, (int)iter,
+                                     ctl.data_ptr<float>(), stats.data_ptr<double>(), stream()),
+           "robust_geomed_finalize");
+}
+
+// Blocks of a robust_pairdist / robust_wmean launch over n floats.
+int64_t robust_dist_grid(int64_t n) { return (int64_t)fd_robust_dist_grid(n); }
+
 // Client-level differential privacy (privacy.hip).  The stream of a call: the 64-bit seed as two
 // 32-bit words, the round and the client (one Philox counter word each), and first4, the float4 index
 // of the tensor's first element in that stream.
@@ -2432,6 +2550,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("robust_agg", &robust_agg, py::arg("srcs"), py::arg("k"), py::arg("out"), py::arg("shadow") = py::none(),
         py::arg("counts") = py::none());
   m.def("robust_agg_grid", &robust_agg_grid);
+  m.def("robust_pairdist", &robust_pairdist, py::arg("srcs"), py::arg("partial"));
+  m.def("robust_krum_finalize", &robust_krum_finalize, py::arg("partial"), py::arg("grid"), py::arg("M"), py::arg("f"),
+        py::arg("m"), py::arg("ctl"), py::arg("stats"));
+  m.def("robust_wmean", &robust_wmean, py::arg("srcs"), py::arg("ctl"), py::arg("out") = py::none(),
+        py::arg("shadow") = py::none(), py::arg("partial") = py::none());
+  m.def("robust_geomed_finalize", &robust_geomed_finalize, py::arg("partial"), py::arg("grid"), py::arg("M"),
+        py::arg("nu"), py::arg("iter"), py::arg("ctl"), py::arg("stats"));
+  m.def("robust_dist_grid", &robust_dist_grid);
   m.def("privacy_grid", &privacy_grid);
   m.def("privacy_norm", &privacy_norm, py::arg("w"), py::arg("anchor"), py::arg("partial"), py::arg("stats"),
         py::arg("clip"));

@@ -709,6 +709,75 @@ int fd_robust_agg(const float* const* src, int M, int k, float* out, void* shado
   }
   return 0;
 }
+// (the grid of fd_server_opt -- csrc/kernels/robust_dist.hip rd_grid_for)
+int fd_robust_dist_grid(long long n) { return fd_server_opt_grid(n); }
+int fd_robust_pairdist(const float* const* src, int M, double* partial, long long n, hipStream_t) {
+  ++hc::calls;
+  // the kernel reads n / 4 float4 of each of the M sources and writes M (M - 1) / 2 doubles per block
+  if (n <= 0 || n % 4 != 0) hc::violations.push_back("robust_pairdist: n % 4");
+  if (M < 2 || M > 16 || !src) {
+    hc::violations.push_back("robust_pairdist: M");
+    return 0;
+  }
+  for (int s = 0; s < M; ++s) hc::span(src[s], n * 4, "robust_pairdist source");
+  hc::span(partial, 8LL * (M * (M - 1) / 2) * fd_robust_dist_grid(n), "robust_pairdist partial");
+  return 0;
+}
+int fd_robust_krum_finalize(const double* partial, int grid, int M, int f, int m, float* ctl, double* stats,
+                            hipStream_t) {
+  ++hc::calls;
+  // one block: reads grid rows of M (M - 1) / 2 doubles, writes 20 floats of ctl and 288 doubles of stats
+  if (M < 2 || M > 16 || grid < 1 || grid > 4096) {
+    hc::violations.push_back("robust_krum_finalize: M / grid");
+    return 0;
+  }
+  if (f < 0 || m < 1 || m > M) hc::violations.push_back("robust_krum_finalize: f / m");
+  hc::span(partial, 8LL * grid * (M * (M - 1) / 2), "robust_krum_finalize partial");
+  hc::span(ctl, 20 * 4, "robust_krum_finalize ctl");
+  hc::span(stats, 288 * 8, "robust_krum_finalize stats");
+  return 0;
+}
+int fd_robust_wmean(const float* const* src, int M, const float* ctl, float* out, void* shadow, double* partial,
+                    long long n, hipStream_t) {
+  ++hc::calls;
+  // the kernel reads 17 floats of ctl and n / 4 float4 of each source, writes as many to out (uint2 to
+  // the shadow) and M + 1 doubles per block of partial
+  if (n <= 0 || n % 4 != 0) hc::violations.push_back("robust_wmean: n % 4");
+  if (M < 2 || M > 16 || !src) {
+    hc::violations.push_back("robust_wmean: M");
+    return 0;
+  }
+  hc::span(ctl, 20 * 4, "robust_wmean ctl");
+  hc::opt_span(out, n * 4, "robust_wmean out");
+  hc::opt_span(shadow, n * 2, "robust_wmean shadow");
+  hc::opt_span(partial, 8LL * (M + 1) * fd_robust_dist_grid(n), "robust_wmean partial");
+  if (shadow && !out) hc::violations.push_back("robust_wmean: shadow without out");
+  const auto overlaps = [](const void* a, long long ab, const void* b, long long bb) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + (uintptr_t)bb && b0 < a0 + (uintptr_t)ab;
+  };
+  for (int s = 0; s < M; ++s) {
+    hc::span(src[s], n * 4, "robust_wmean source");
+    if (src[s] && out && overlaps(src[s], n * 4, out, n * 4)) hc::violations.push_back("robust_wmean: out overlaps a source");
+    if (src[s] && shadow && overlaps(src[s], n * 4, shadow, n * 2))
+      hc::violations.push_back("robust_wmean: shadow overlaps a source");
+  }
+  return 0;
+}
+int fd_robust_geomed_finalize(const double* partial, int grid, int M, double nu, int iter, float* ctl, double* stats,
+                              hipStream_t) {
+  ++hc::calls;
+  // one block: reads grid rows of M + 1 doubles, writes 20 floats of ctl and row iter (34 doubles) of stats
+  if (M < 2 || M > 16 || grid < 1 || grid > 4096 || iter < 0) {
+    hc::violations.push_back("robust_geomed_finalize: M / grid / iter");
+    return 0;
+  }
+  if (!std::isfinite(nu) || !(nu > 0.0)) hc::violations.push_back("robust_geomed_finalize: nu");
+  hc::span(partial, 8LL * grid * (M + 1), "robust_geomed_finalize partial");
+  hc::span(ctl, 20 * 4, "robust_geomed_finalize ctl");
+  hc::span(stats ? stats + 34LL * iter : nullptr, 34 * 8, "robust_geomed_finalize stats row");
+  return 0;
+}
 // (the grid of fd_server_opt -- csrc/kernels/privacy.hip pv_grid_for)
 int fd_privacy_grid(long long n) { return fd_server_opt_grid(n); }
 namespace {
@@ -1630,6 +1699,93 @@ int main() {
     expect_ok("robust_agg out beside a source", [&] { robust_agg({s3[0], lo, s3[2]}, 1, hi, sh, ct); });
     auto shv = big.narrow(0, n / 2, n / 2).view(bf);
     expect_reject("robust_agg shadow overlaps a source", [&] { robust_agg({s3[0], lo, s3[2]}, 1, out, shv, ct); });
+  }
+  // ---- distance-based robust aggregation: M fp32 sources, fp64 partials, 20 ctl floats, fp64 stats
+  {
+    const auto f64 = at::kDouble;
+    const int64_t n = 4096 * 1024 + 4 * 257;  // the grid-stride loop wraps, ragged last block
+    const int64_t grid = fd_robust_dist_grid(n);
+    std::vector<at::Tensor> s3, s16, s17;
+    for (int i = 0; i < 17; ++i) {
+      auto t = T_({n}, f32);
+      if (i < 3) s3.push_back(t);
+      if (i < 16) s16.push_back(t);
+      s17.push_back(t);
+    }
+    auto p3 = T_({3 * grid}, f64), p16 = T_({120 * grid}, f64), w3 = T_({4 * grid}, f64), w16 = T_({17 * grid}, f64);
+    auto ctl = T_({20}, f32), ks = T_({288}, f64), gs = T_({7 * 34}, f64);
+    auto out = T_({n}, f32), sh = T_({n}, bf);
+    expect_ok("robust_pairdist M 3", [&] { robust_pairdist(s3, p3); });
+    expect_ok("robust_pairdist M 16", [&] { robust_pairdist(s16, p16); });
+    expect_ok("robust_pairdist M 2", [&] { robust_pairdist({s3[0], s3[1]}, p3); });
+    expect_reject("robust_pairdist M 1", [&] { robust_pairdist({s3[0]}, p3); });
+    expect_reject("robust_pairdist M 17", [&] { robust_pairdist(s17, p16); });
+    expect_reject("robust_pairdist short partial", [&] { robust_pairdist(s16, T_({120 * grid - 1}, f64)); });
+    expect_reject("robust_pairdist partial dtype", [&] { robust_pairdist(s3, T_({3 * grid}, f32)); });
+    auto srt = T_({n - 4}, f32), sb = T_({n}, bf);
+    expect_reject("robust_pairdist short source", [&] { robust_pairdist({s3[0], srt, s3[2]}, p3); });
+    expect_reject("robust_pairdist source dtype", [&] { robust_pairdist({s3[0], sb, s3[2]}, p3); });
+    auto xt = T_({2, n / 2}, f32).t();
+    expect_reject("robust_pairdist non-contiguous source", [&] { robust_pairdist({s3[0], s3[1], xt}, p3); });
+    std::vector<at::Tensor> s6;
+    for (int i = 0; i < 3; ++i) s6.push_back(T_({2046}, f32));
+    expect_reject("robust_pairdist numel % 4", [&] { robust_pairdist(s6, p3); });
+
+    expect_ok("robust_krum_finalize M 3", [&] { robust_krum_finalize(p3, grid, 3, 0, 3, ctl, ks); });
+    expect_ok("robust_krum_finalize M 16", [&] { robust_krum_finalize(p16, grid, 16, 6, 10, ctl, ks); });
+    expect_ok("robust_krum_finalize large f", [&] { robust_krum_finalize(p3, grid, 3, 40, 1, ctl, ks); });
+    expect_reject("robust_krum_finalize M 1", [&] { robust_krum_finalize(p3, grid, 1, 0, 1, ctl, ks); });
+    expect_reject("robust_krum_finalize M 17", [&] { robust_krum_finalize(p16, grid, 17, 0, 1, ctl, ks); });
+    expect_reject("robust_krum_finalize f < 0", [&] { robust_krum_finalize(p3, grid, 3, -1, 1, ctl, ks); });
+    expect_reject("robust_krum_finalize m 0", [&] { robust_krum_finalize(p3, grid, 3, 0, 0, ctl, ks); });
+    expect_reject("robust_krum_finalize m > M", [&] { robust_krum_finalize(p3, grid, 3, 0, 4, ctl, ks); });
+    expect_reject("robust_krum_finalize grid 0", [&] { robust_krum_finalize(p3, 0, 3, 0, 1, ctl, ks); });
+    expect_reject("robust_krum_finalize grid past partial", [&] { robust_krum_finalize(p3, grid + 1, 3, 0, 1, ctl, ks); });
+    expect_reject("robust_krum_finalize M past partial", [&] { robust_krum_finalize(p3, grid, 4, 0, 1, ctl, ks); });
+    expect_reject("robust_krum_finalize short ctl", [&] { robust_krum_finalize(p3, grid, 3, 0, 1, T_({19}, f32), ks); });
+    expect_reject("robust_krum_finalize short stats", [&] { robust_krum_finalize(p3, grid, 3, 0, 1, ctl, T_({287}, f64)); });
+    expect_reject("robust_krum_finalize ctl dtype", [&] { robust_krum_finalize(p3, grid, 3, 0, 1, T_({20}, f64), ks); });
+    expect_reject("robust_krum_finalize stats dtype", [&] { robust_krum_finalize(p3, grid, 3, 0, 1, ctl, T_({288}, f32)); });
+
+    expect_ok("robust_wmean M 3", [&] { robust_wmean(s3, ctl, out, sh, w3); });
+    expect_ok("robust_wmean M 16", [&] { robust_wmean(s16, ctl, out, sh, w16); });
+    expect_ok("robust_wmean distances only", [&] { robust_wmean(s3, ctl, none, none, w3); });
+    expect_ok("robust_wmean out only", [&] { robust_wmean(s3, ctl, out, none, none); });
+    expect_reject("robust_wmean M 1", [&] { robust_wmean({s3[0]}, ctl, out, sh, w3); });
+    expect_reject("robust_wmean M 17", [&] { robust_wmean(s17, ctl, out, sh, w16); });
+    expect_reject("robust_wmean shadow without out", [&] { robust_wmean(s3, ctl, none, sh, w3); });
+    expect_reject("robust_wmean short ctl", [&] { robust_wmean(s3, T_({16}, f32), out, sh, w3); });
+    expect_reject("robust_wmean short out", [&] { robust_wmean(s3, ctl, srt, none, w3); });
+    expect_reject("robust_wmean short shadow", [&] { robust_wmean(s3, ctl, out, T_({n - 4}, bf), w3); });
+    expect_reject("robust_wmean short partial", [&] { robust_wmean(s3, ctl, out, sh, T_({4 * grid - 1}, f64)); });
+    expect_reject("robust_wmean short source", [&] { robust_wmean({s3[0], srt, s3[2]}, ctl, out, sh, w3); });
+    expect_reject("robust_wmean out dtype", [&] { robust_wmean(s3, ctl, sb, sh, w3); });
+    expect_reject("robust_wmean shadow dtype", [&] { robust_wmean(s3, ctl, out, T_({n}, f32), w3); });
+    expect_reject("robust_wmean partial dtype", [&] { robust_wmean(s3, ctl, out, sh, T_({4 * grid}, f32)); });
+    expect_reject("robust_wmean ctl dtype", [&] { robust_wmean(s3, T_({20}, f64), out, sh, w3); });
+    expect_reject("robust_wmean non-contiguous source", [&] { robust_wmean({s3[0], s3[1], xt}, ctl, out, sh, w3); });
+    expect_reject("robust_wmean numel % 4", [&] { robust_wmean(s6, ctl, T_({2046}, f32), none, none); });
+    expect_reject("robust_wmean out is a source", [&] { robust_wmean(s3, ctl, s3[1], sh, w3); });
+    auto big = T_({2 * n}, f32);
+    auto lo = big.narrow(0, 0, n), mid = big.narrow(0, n / 2, n), hi = big.narrow(0, n, n);
+    expect_reject("robust_wmean out overlaps a source", [&] { robust_wmean({s3[0], lo, s3[2]}, ctl, mid, sh, w3); });
+    expect_ok("robust_wmean out beside a source", [&] { robust_wmean({s3[0], lo, s3[2]}, ctl, hi, sh, w3); });
+    auto shv = big.narrow(0, n / 2, n / 2).view(bf);
+    expect_reject("robust_wmean shadow overlaps a source", [&] { robust_wmean({s3[0], lo, s3[2]}, ctl, out, shv, w3); });
+
+    expect_ok("robust_geomed_finalize row 0", [&] { robust_geomed_finalize(w3, grid, 3, 1e-6, 0, ctl, gs); });
+    expect_ok("robust_geomed_finalize last row", [&] { robust_geomed_finalize(w16, grid, 16, 1e-6, 6, ctl, gs); });
+    expect_reject("robust_geomed_finalize row past stats", [&] { robust_geomed_finalize(w3, grid, 3, 1e-6, 7, ctl, gs); });
+    expect_reject("robust_geomed_finalize iter < 0", [&] { robust_geomed_finalize(w3, grid, 3, 1e-6, -1, ctl, gs); });
+    expect_reject("robust_geomed_finalize nu 0", [&] { robust_geomed_finalize(w3, grid, 3, 0.0, 0, ctl, gs); });
+    expect_reject("robust_geomed_finalize nu < 0", [&] { robust_geomed_finalize(w3, grid, 3, -1e-6, 0, ctl, gs); });
+    expect_reject("robust_geomed_finalize nu NaN", [&] { robust_geomed_finalize(w3, grid, 3, std::nan(""), 0, ctl, gs); });
+    expect_reject("robust_geomed_finalize nu inf", [&] { robust_geomed_finalize(w3, grid, 3, HUGE_VAL, 0, ctl, gs); });
+    expect_reject("robust_geomed_finalize M 17", [&] { robust_geomed_finalize(w16, grid, 17, 1e-6, 0, ctl, gs); });
+    expect_reject("robust_geomed_finalize M past partial", [&] { robust_geomed_finalize(w3, grid, 4, 1e-6, 0, ctl, gs); });
+    expect_reject("robust_geomed_finalize grid 4097", [&] { robust_geomed_finalize(w16, 4097, 3, 1e-6, 0, ctl, gs); });
+    expect_reject("robust_geomed_finalize short ctl", [&] { robust_geomed_finalize(w3, grid, 3, 1e-6, 0, T_({19}, f32), gs); });
+    expect_reject("robust_geomed_finalize stats dtype", [&] { robust_geomed_finalize(w3, grid, 3, 1e-6, 0, ctl, T_({34}, f32)); });
   }
   // ---- client-level privacy: w / anchor fp32, the bf16 shadow, one double per block, 4 stats floats
   {

@@ -18,7 +18,7 @@ from typing import Optional
 
 
 _OPTIONAL_INTS = ("drop_client", "drop_round", "num_clients", "poison_client", "poison_round", "privacy_seed",
-                  "secagg_seed")
+                  "secagg_seed", "byzantine", "krum_select")
 
 
 @dataclass
@@ -78,8 +78,15 @@ class FedConfig:
     # Byzantine-robust aggregation (parallel/robust.py; Yin et al., ICML 2018): per coordinate the k
     # lowest and k highest client values are dropped.  "mean": the plain mean (reference);
     # "trimmed_mean": k = floor(trim_ratio * M) of the M participating clients; "median": k = (M - 1) // 2
-    aggregator: str = "mean"                # "mean" | "trimmed_mean" | "median"
+    # Distance-based kinds (parallel/robust_dist.py): "multi_krum" (Blanchard et al., NeurIPS 2017) averages the
+    # m clients closest to their M - f - 2 nearest neighbours and names the rest; "geometric_median" (RFA,
+    # Pillutla et al. 2022) runs smoothed Weiszfeld iterations and gives every client a weight
+    aggregator: str = "mean"                # "mean" | "trimmed_mean" | "median" | "multi_krum" | "geometric_median"
     trim_ratio: float = 0.2                 # trimmed_mean: share trimmed at each end, in [0, 0.5)
+    byzantine: Optional[int] = None         # multi_krum: f, the liars to tolerate; None: (M - 3) // 2 of the live M
+    krum_select: Optional[int] = None       # multi_krum: m, the clients averaged; None: M - f (1: Krum proper)
+    geomed_iters: int = 6                   # geometric_median: Weiszfeld iterations
+    geomed_nu: float = 1e-6                 # geometric_median: smoothing, the floor of a distance
     # Client-level differential privacy (parallel/privacy.py; DP-FedAvg, McMahan et al., ICLR 2018): every
     # sampled client clips its round update w - w_global to L2 norm privacy_clip and adds
     # N(0, (privacy_noise * privacy_clip)^2 / M) before the exchange, M the round's sampled clients.  0: off

@@ -34,7 +34,7 @@ from ..parallel.compress import check_compress_config, make_compressor
 from ..parallel.fedavg import broadcast_model, fedavg_
 from ..parallel.privacy import check_privacy_config, make_privatizer
 from ..parallel.secagg import check_secagg_config, make_secagg
-from ..parallel.robust import check_robust_config, make_robust, most_trimmed, robust_aggregate_
+from ..parallel.robust import DIST_AGGREGATORS, check_robust_config, make_robust, most_trimmed, robust_aggregate_
 from ..parallel.server_opt import check_server_config, make_server_optimizer
 from ..utils import checkpoint as ck
 from ..utils import faults
@@ -190,7 +190,8 @@ class FederatedClient:
         self.robust = make_robust(cfg, self.topo.gpus_per_client)
         if self.robust is not None:
             log.info(f"robust aggregation: {self.robust.aggregator}"
-                     + (f" (trim_ratio {self.robust.trim_ratio:g})" if self.robust.aggregator == "trimmed_mean" else ""))
+                     + (f" (trim_ratio {self.robust.trim_ratio:g})" if self.robust.aggregator == "trimmed_mean" else "")
+                     + _dist_setup_note(self.robust))
         # Client-level differential privacy (parallel/privacy.py; None: privacy_clip == 0, today's path)
         self.privacy = make_privatizer(cfg, self.topo.gpus_per_client)
         if self.privacy is not None:
@@ -414,7 +415,7 @@ class FederatedClient:
                      f"|step| = {norms['step_l2']:.6g}")
         trim = self.robust.last if self.robust is not None and total_w > 0 else None
         if trim is not None:
-            log.info(_trim_line(trim))
+            log.info(_robust_line(trim))
         comp = _compress_fields(self.compress.last) if self.compress is not None and self.compress.last else None
         if comp is not None:
             log.info(_compress_sent_line(comp))
@@ -448,7 +449,7 @@ class FederatedClient:
         if norms is not None:
             rec.update(delta_l2=norms["delta_l2"], step_l2=norms["step_l2"])
         if trim is not None:
-            rec.update(trimmed_share=trim["trimmed_share"], k=trim["k"])
+            rec.update(_robust_fields(trim))
         if comp is not None:  # (after the trim keys, before privacy's: update_l2 is privacy's when both are on)
             rec.update(comp)
         if sec is not None:  # (likewise: update_l2 is privacy's when both are on)
@@ -522,6 +523,9 @@ class FederatedClient:
             # spent over the whole run, without subsampling amplification: an upper bound
             rep.update(privacy_epsilon=self.privacy.epsilon(self.cfg.rounds), privacy_delta=self.privacy.delta,
                        privacy_clip=self.privacy.clip, privacy_noise=self.privacy.noise_multiplier)
+        robust = getattr(self, "robust", None)
+        if robust is not None and robust.last is not None and "kind" in robust.last:
+            rep["robust"] = robust.last  # the last round's multi-Krum / geometric-median report
         if self.di.is_main:
             path = os.path.join(self.cfg.out_dir, "federated_report.json")
             with open(path, "w") as f:
@@ -601,6 +605,39 @@ def _trim_line(trim: Dict) -> str:
     j, share = most_trimmed(trim)
     return (f"robust aggregate of {trim['clients']} client(s), k = {trim['k']}: most trimmed is participant "
             f"{j + 1} with share {share:.4f} (honest expectation {2 * trim['k'] / max(trim['clients'], 1):.4f})")
+
+
+def _dist_setup_note(robust) -> str:
+    if robust.aggregator == "multi_krum":
+        f = "(M - 3) // 2" if robust.byzantine is None else str(robust.byzantine)
+        return f" (byzantine f = {f}, krum_select m = {'M - f' if robust.krum_select is None else robust.krum_select})"
+    if robust.aggregator == "geometric_median":
+        return f" ({robust.geomed_iters} Weiszfeld iterations, nu {robust.geomed_nu:g})"
+    return ""
+
+
+def _robust_fields(trim: Dict) -> Dict:
+    """A record's robust-aggregation keys: the trimmed shares of the coordinate-wise kinds, the whole
+    report (under ``robust``) of the distance-based ones."""
+    if "kind" in trim:
+        return {"robust": trim}
+    return {"trimmed_share": trim["trimmed_share"], "k": trim["k"]}
+
+
+def _robust_line(trim: Dict) -> str:
+    """One log line for a robust round, by the report's kind: the rejected participants (multi-Krum), the
+    lowest-weight participant beside the uniform 1 / M (geometric median), or ``_trim_line``."""
+    kind = trim.get("kind")
+    if kind == "multi_krum":
+        rej = ", ".join(f"{j + 1} (score {trim['scores'][j]:.6g})" for j in trim["rejected"]) or "none"
+        return (f"multi-Krum of {trim['clients']} client(s), f = {trim['f']}, m = {trim['m']}: rejected "
+                f"participant(s) {rej}")
+    if kind == "geometric_median":
+        w = trim["weights"]
+        j = min(range(len(w)), key=lambda i: (w[i], i))
+        return (f"geometric median of {trim['clients']} client(s), {trim['iters']} iteration(s): lowest weight is "
+                f"participant {j + 1} with {w[j]:.6f} (uniform {1.0 / max(trim['clients'], 1):.6f})")
+    return _trim_line(trim)
 
 
 @torch.no_grad()
@@ -686,7 +723,9 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
     With a robust aggregator (``cfg.aggregator``, parallel/robust.py) ``robust_aggregate_`` takes the
     place of ``_average_masters`` -- the call ``fedavg_(..., robust=)`` makes on the gathered rows -- and
     each round's record carries ``trimmed_share`` / ``k`` (tests/test_robust_agg_cpu.py: equal to the
-    3-rank gloo run bit for bit).  A poisoned client (``cfg.poison_client``, utils/faults.py) sends a
+    3-rank gloo run bit for bit); the distance-based kinds (parallel/robust_dist.py) go through
+    ``robust.aggregate_`` and the record carries their report under ``robust``
+    (tests/test_robust_dist_cpu.py).  A poisoned client (``cfg.poison_client``, utils/faults.py) sends a
     changed copy of its weights; its local metrics are those of the weights it trained.
 
     With client-level privacy (``cfg.privacy_clip``, parallel/privacy.py) every client's copy is clipped
@@ -821,7 +860,10 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
         t0 = time.perf_counter()
         norms = trim = None
         if robust is not None:
-            trim = robust_aggregate_(model, locals_, robust.k(len(locals_)), server)
+            if robust.aggregator in DIST_AGGREGATORS:
+                trim = robust.aggregate_(model, locals_, server)
+            else:
+                trim = robust_aggregate_(model, locals_, robust.k(len(locals_)), server)
             norms = server.last if server is not None else None
         elif compress is not None:
             compress.decode_mean_(model, payloads, glob, server)
@@ -851,9 +893,9 @@ def run_virtual_clients(client: "FederatedClient", n_clients: int = 2, rounds: i
         if norms is not None:  # the server step: how far the average drifted, how far the server moved
             hist[-1].update(delta_l2=norms["delta_l2"], step_l2=norms["step_l2"])
         if trim is not None:  # how often each client's value was the one trimmed (parallel/robust.py)
-            hist[-1].update(trimmed_share=trim["trimmed_share"], k=trim["k"])
-            client.log.info(_trim_line(trim))
-            say(f"round {r + 1}/{rounds} " + _trim_line(trim))
+            hist[-1].update(_robust_fields(trim))
+            client.log.info(_robust_line(trim))
+            say(f"round {r + 1}/{rounds} " + _robust_line(trim))
         if compress is not None:
             up = math.sqrt(sum(c["update_l2"] ** 2 for c in recs)) if privacy is None else None
             er = math.sqrt(sum(c["quant_error_l2"] ** 2 for c in recs))

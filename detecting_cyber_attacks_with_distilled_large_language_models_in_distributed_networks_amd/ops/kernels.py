@@ -1169,6 +1169,48 @@ def robust_agg(srcs, k, out, shadow=None, counts=None):
     ext().robust_agg(list(srcs), int(k), out, shadow, counts)
 
 
+ROBUST_DIST_CTL = 20         # ctl floats: the slots' weights in [0..15], the flag in [16]
+ROBUST_KRUM_STATS = 288      # doubles: D as 16 x 16, the scores [256..271], the selected mask [272..287]
+ROBUST_GEOMED_ROW = 34       # doubles per pass: objective, non-finite outputs, Dz [2..17], beta [18..33]
+
+
+def robust_dist_grid(n):
+    """Blocks of a ``robust_pairdist`` / ``robust_wmean`` launch over ``n`` floats (their ``partial``
+    buffers hold M (M - 1) / 2 and M + 1 doubles per block)."""
+    return int(ext().robust_dist_grid(int(n)))
+
+
+def robust_pairdist(srcs, partial):
+    """Per-block sums of the pairwise squared distances of the M = len(srcs) flat fp32 tensors
+    (robust_dist.hip; the oracle is ``parallel.robust_dist.torch_pair_sqdist``): ``partial`` (fp64,
+    >= M (M - 1) / 2 * ``robust_dist_grid(n)``) is [block][pair], pair (i < j) at
+    i (2M - i - 1) / 2 + (j - i - 1); every entry is written on every launch.  2 <= M <= 16."""
+    ext().robust_pairdist(list(srcs), partial)
+
+
+def robust_krum_finalize(partial, grid, M, f, m, ctl, stats):
+    """One block: the pair sums of ``robust_pairdist``'s ``grid`` blocks become D, and
+    ``parallel.robust_dist.krum_select(D, f, m)`` is written to ``ctl`` (fp32, 20: the weights, the
+    flag in [16]) and ``stats`` (fp64, 288: D as 16 x 16, the scores, the selected mask)."""
+    ext().robust_krum_finalize(partial, int(grid), int(M), int(f), int(m), ctl, stats)
+
+
+def robust_wmean(srcs, ctl, out=None, shadow=None, partial=None):
+    """``out`` = the weighted sum of the sources with the weights in ``ctl`` (read on the device; a slot
+    with weight 0 is skipped, ``parallel.robust_dist.torch_weighted_mean_``), ``shadow`` = bf16(out);
+    without ``out`` neither is stored.  ``partial`` (fp64, >= (M + 1) * ``robust_dist_grid(n)``):
+    [block][M + 1], every slot's squared distance to the aggregate, then the non-finite outputs.  A
+    non-zero ``ctl[16]`` makes the launch write nothing.  ``out`` / ``shadow`` must not overlap a source."""
+    ext().robust_wmean(list(srcs), ctl, out, shadow, partial)
+
+
+def robust_geomed_finalize(partial, grid, M, nu, iter, ctl, stats):
+    """One block: the distance sums of ``robust_wmean``'s ``grid`` blocks become Dz, and
+    ``parallel.robust_dist.geomed_weights(Dz, nu)`` is written to ``ctl`` (the next pass's weights, the
+    flag) and to row ``iter`` of ``stats`` (fp64, rows of 34: objective, non-finite outputs, Dz, beta)."""
+    ext().robust_geomed_finalize(partial, int(grid), int(M), float(nu), int(iter), ctl, stats)
+
+
 def _seed_words(seed):
     seed = int(seed)
     if not 0 <= seed < 1 << 64:

@@ -178,19 +178,19 @@ def _fedopt_(model, weight: float, participate: bool, comm, server) -> float:
 def _robust_(model, participate: bool, comm, server, robust) -> float:
     """``fedavg_`` with a robust aggregator (parallel/robust.py): every rank learns the live set from
     an all-reduced flag vector (one slot per rank), the masters are all-gathered, the rows of the
-    participating clients (replica 0 of each, in client order) go through ``robust_aggregate_`` --
-    one fused pass on the GPU -- and, with a server optimizer, its step follows.  A client that does
-    not participate contributes no row and still receives the aggregate; every rank computes the same
-    aggregate from the same rows, so the ranks stay identical.
+    participating clients (replica 0 of each, in client order) go through ``robust.aggregate_`` --
+    one fused pass on the GPU for the coordinate-wise kinds, a few for the distance-based ones -- and,
+    with a server optimizer, its step follows.  A client that does not participate contributes no row
+    and still receives the aggregate; every rank computes the same aggregate from the same rows, so
+    the ranks stay identical.
 
     Memory: the gather buffer is ``world x`` the master -- for DistilBERT (265 MB of fp32 master)
     2.1 GB at 8 ranks -- and lives for this call only."""
-    from .robust import robust_aggregate_
     A = model.arena
     if not _dist_on():
         if not participate:
             return 0.0
-        robust.last = robust_aggregate_(model, [A.master.clone()], 0, server)  # one client: its own weights
+        robust.last = robust.aggregate_(model, [A.master.clone()], server)  # one client: its own weights
         return 1.0
     world, rank = dist.get_world_size(), dist.get_rank()
     dev = A.master.device
@@ -214,7 +214,7 @@ def _robust_(model, participate: bool, comm, server, robust) -> float:
             dist.all_gather_into_tensor(rows, A.master)
         else:
             dist.all_gather(list(rows.unbind(0)), A.master)
-    robust.last = robust_aggregate_(model, [rows[c * g] for c in live], robust.k(len(live)), server)
+    robust.last = robust.aggregate_(model, [rows[c * g] for c in live], server)
     del rows
     return float(len(live))
 

@@ -34,7 +34,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
-AGGREGATORS = ("mean", "trimmed_mean", "median")
+AGGREGATORS = ("mean", "trimmed_mean", "median", "multi_krum", "geometric_median")
+DIST_AGGREGATORS = ("multi_krum", "geometric_median")  # judged by L2 distance: parallel/robust_dist.py
 MAX_GPU_CLIENTS = 16  # the kernel's instantiations: 2 <= M <= 16
 _CHUNK = 1 << 22      # coordinates per pass of the reference (bounds its int64 temporaries)
 
@@ -93,13 +94,19 @@ def trim_count(M: int, aggregator: str, trim_ratio: float = 0.2) -> int:
         return (M - 1) // 2
     if aggregator == "mean":
         return 0
+    if aggregator in DIST_AGGREGATORS:
+        raise ValueError(f"aggregator {aggregator!r} has no trim count: it judges whole updates by their distance")
     if aggregator != "trimmed_mean":
-        raise ValueError(f"aggregator must be one of {', '.join(AGGREGATORS)}; got {aggregator!r}")
+        raise ValueError(f"aggregator must be one of {', '.join(AGGREGATORS)}; got {aggregator!r}{_krum_hint(aggregator)}")
     r = _check_ratio(trim_ratio)
     k = int(math.floor(r * M))
     if 2 * k >= M:
         raise ValueError(f"trim_ratio={r!r} trims {k} of {M} clients at each end and leaves none")
     return k
+
+
+def _krum_hint(aggregator) -> str:
+    return " (Krum proper is aggregator='multi_krum' with krum_select=1)" if str(aggregator).lower() == "krum" else ""
 
 
 def _check_ratio(trim_ratio) -> float:
@@ -114,16 +121,31 @@ def _check_ratio(trim_ratio) -> float:
 
 @dataclass
 class RobustAggregator:
-    """What ``fedavg_(..., robust=)`` takes: the aggregator ("trimmed_mean" | "median"), its
-    ``trim_ratio``, and how many consecutive ranks make one client.  ``last`` is the latest round's
-    report (``robust_aggregate_``'s dict), as ``ServerOptimizer.last`` holds its norms."""
+    """What ``fedavg_(..., robust=)`` takes: the aggregator ("trimmed_mean" | "median" | "multi_krum" |
+    "geometric_median"), its parameters, and how many consecutive ranks make one client.  ``last`` is the
+    latest round's report (``robust_aggregate_``'s or ``robust_dist_aggregate_``'s dict), as
+    ``ServerOptimizer.last`` holds its norms."""
     aggregator: str
     trim_ratio: float = 0.2
     gpus_per_client: int = 1
     last: Optional[Dict] = None
+    byzantine: Optional[int] = None    # multi_krum: f (None: the most Krum tolerates for the round's M)
+    krum_select: Optional[int] = None  # multi_krum: m (None: M - f)
+    geomed_iters: int = 6
+    geomed_nu: float = 1e-6
 
     def k(self, M: int) -> int:
         return trim_count(M, self.aggregator, self.trim_ratio)
+
+    def aggregate_(self, model, states: Sequence[torch.Tensor], server=None) -> Dict:
+        """The round's aggregate of ``states`` into the model (and the server step, if any): the
+        coordinate-wise kinds through ``robust_aggregate_`` with this round's ``k``, the distance-based
+        ones through ``robust_dist_aggregate_``.  Returns the round's report."""
+        if self.aggregator in DIST_AGGREGATORS:
+            from .robust_dist import robust_dist_aggregate_
+            return robust_dist_aggregate_(model, states, self.aggregator, server, self.byzantine, self.krum_select,
+                                          self.geomed_iters, self.geomed_nu)
+        return robust_aggregate_(model, states, self.k(len(states)), server)
 
 
 def check_robust_config(cfg) -> Optional[str]:
@@ -132,11 +154,13 @@ def check_robust_config(cfg) -> Optional[str]:
     callers refuse a bad configuration before any work."""
     agg = str(getattr(cfg, "aggregator", "mean")).lower()
     if agg not in AGGREGATORS:
-        raise ValueError(f"aggregator must be one of {', '.join(AGGREGATORS)}; got {cfg.aggregator!r}")
+        raise ValueError(f"aggregator must be one of {', '.join(AGGREGATORS)}; got {cfg.aggregator!r}{_krum_hint(agg)}")
     if agg == "mean":
         return None
     if agg == "trimmed_mean":
         _check_ratio(cfg.trim_ratio)
+    if agg in DIST_AGGREGATORS:
+        _check_dist_fields(cfg)
     if getattr(cfg, "transport", "collective") == "tcp":
         raise ValueError(f"aggregator={agg!r} needs transport='collective': the reference-compatible TCP server "
                          f"keeps the reference's plain mean")
@@ -145,13 +169,33 @@ def check_robust_config(cfg) -> Optional[str]:
     return agg
 
 
+def _check_dist_fields(cfg) -> None:
+    f, m = getattr(cfg, "byzantine", None), getattr(cfg, "krum_select", None)
+    if f is not None and int(f) < 0:
+        raise ValueError(f"byzantine must be >= 0, got {f!r}")
+    if m is not None and int(m) < 1:
+        raise ValueError(f"krum_select must be >= 1, got {m!r}")
+    if int(getattr(cfg, "geomed_iters", 6)) < 1:
+        raise ValueError(f"geomed_iters must be >= 1, got {cfg.geomed_iters!r}")
+    try:
+        nu = float(getattr(cfg, "geomed_nu", 1e-6))
+    except (TypeError, ValueError):
+        raise ValueError(f"geomed_nu must be a positive finite number, got {cfg.geomed_nu!r}") from None
+    if not (math.isfinite(nu) and nu > 0.0):
+        raise ValueError(f"geomed_nu must be positive and finite, got {cfg.geomed_nu!r}")
+
+
 def make_robust(cfg, gpus_per_client: int = 1) -> Optional[RobustAggregator]:
     """The configuration's ``RobustAggregator`` (``--aggregator median``), or None for the plain mean
     (``aggregator="mean"``: today's path, untouched)."""
     agg = check_robust_config(cfg)
     if agg is None:
         return None
-    return RobustAggregator(agg, float(cfg.trim_ratio), int(gpus_per_client))
+    f, m = getattr(cfg, "byzantine", None), getattr(cfg, "krum_select", None)
+    return RobustAggregator(agg, float(cfg.trim_ratio), int(gpus_per_client),
+                            byzantine=None if f is None else int(f), krum_select=None if m is None else int(m),
+                            geomed_iters=int(getattr(cfg, "geomed_iters", 6)),
+                            geomed_nu=float(getattr(cfg, "geomed_nu", 1e-6)))
 
 
 def _report(trimmed: List[int], nonfinite: int, k: int, n: int) -> Dict:
